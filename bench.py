@@ -8,7 +8,13 @@ filter_grep (Regex code ^5\\d\\d$)] -- flbgpu_filter_chain_run_dev, which runs t
 are evaluated on the capture spans and only the kept records are written (fused_kernels.inc; SURVEY 8(d)
 "fused": 552 + 275 x keep algorithmic bytes per record).
 
-    python bench.py --gpus N --steps K --warmup W [--records R]
+    python bench.py --gpus N --steps K --warmup W [--records R] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step, kernels, roofline
+from the committed PMC summary).  --full adds everything else the line can carry: the CPU baselines, the checks of the
+timed output against the unfused kernels / the oracle / the reference, the side measurements (`secondary`) and the
+rocprofv3 passes a stale PMC summary calls for.  --dump-outputs DIR writes what the last timed step returned (see
+dump_outputs) as .npy files; the inputs are seeded, so two builds can be compared output for output.
 
 For N > 1 the driver launches one rank per GPU with torch.distributed.run; every rank filters its
 own shard (records are independent: no data-path collective, weak scaling), the timed region is
@@ -1156,6 +1162,37 @@ def verify_timed_output(g, L, data, off, n, fused_host, parsed_chunk, fgrep, arg
     return out
 
 
+DUMP_SAMPLE_ROWS = 16384
+DUMP_MAX_BYTE_VALUES = 12 << 20        # 48 MB of float32 at most for the sampled rows' bytes
+
+
+def dump_outputs(out_dir, kb, koff, n, kept_records):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last step -- the output chunk (kb: the kept
+    records' bytes) and its row offsets (koff: one row per input record, an empty row for a dropped one) -- as .npy files
+    in float32 / float64.  The whole output would be GBs of floats, so: the totals, a histogram of every output byte, and
+    a fixed seeded sample of rows (their indices, offsets, lengths and bytes)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rng = np.random.default_rng(0xB5EED)
+    rows = np.sort(rng.choice(n, size=min(n, DUMP_SAMPLE_ROWS), replace=False)).astype(np.int64)
+    start = koff[rows].astype(np.int64)
+    lens = koff[rows + 1].astype(np.int64) - start
+    # whole rows of the sample while their bytes fit the cap (at the default workload they all do)
+    fit = int(np.searchsorted(np.cumsum(lens), DUMP_MAX_BYTE_VALUES, side="right"))
+    base = start[:fit] - (np.cumsum(lens[:fit]) - lens[:fit])          # row start minus its place in the concatenation
+    idx = np.repeat(base, lens[:fit]) + np.arange(int(lens[:fit].sum()))
+    arrays = {
+        "totals": np.array([n, kb.nbytes, kept_records, int(np.count_nonzero(np.diff(koff.astype(np.int64))))], dtype=np.float64),
+        "byte_histogram": np.bincount(kb, minlength=256).astype(np.float64),
+        "sample_rows": rows.astype(np.float64),
+        "sample_row_offsets": start.astype(np.float64),
+        "sample_row_lengths": lens.astype(np.float64),
+        "sample_row_bytes": kb[idx].astype(np.float32),
+    }
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     # stdout carries exactly ONE line (the JSON): libraries that chat on fd 1 (RCCL prints its own path there)
     # are pointed at stderr for the whole run, the line goes to the saved descriptor at the very end
@@ -1174,7 +1211,12 @@ def main():
     ap.add_argument("--pmc", action="store_true", help="measure roofline.traffic now: two more passes of the headline step under rocprofv3 (FETCH_SIZE, WRITE_SIZE)")
     ap.add_argument("--ndjson-lines", type=int, default=100_000_000, help="BASELINE configs[2]: NDJSON lines through JSON -> events -> 32-rule grep (secondary)")
     ap.add_argument("--l2m-records", type=int, default=1_000_000_000, help="BASELINE configs[3]: records through log_to_metrics over all ranks (secondary)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: CPU baselines, checks of the timed output, secondary measurements, "
+                                                        "rocprofv3 passes when the committed PMC summary is stale (a plain run does none of these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` on its own: this process becomes the launcher -- one rank per GPU through
@@ -1198,12 +1240,16 @@ def main():
     # ---- CPU baselines first (rank 0, N = 1), before this process owns a GPU context: the forked workers of the
     #      N-process leg only run the oracle
     cpu = None
-    if not args.no_cpu and world == 1 and rank == 0:
+    if args.full and not args.no_cpu and world == 1 and rank == 0:
         cpu = measure_cpu(data, off, n, args)
 
-    import torch
+    # torch carries the ranks' collectives and the side measurements; a plain one-GPU run needs none of it (its timed
+    # steps end in the library's own device synchronize), so it does not pay for importing it
+    torch = None
+    if world > 1 or args.full or os.environ.get("FLBGPU_BENCH_FORCE_DIST"):
+        import torch
     dist = None
-    ndev = max(1, torch.cuda.device_count())
+    ndev = max(1, torch.cuda.device_count()) if torch is not None else 1
     dev = local_rank % ndev
     shared_gpu = world > ndev              # more ranks than GPUs (a 1-GPU box driving the N-rank path): RCCL refuses two ranks on one
                                            # device, the collectives then run on gloo through the same merge code (fluent_bit_amd.l2m_merge,
@@ -1217,7 +1263,7 @@ def main():
             dist.init_process_group("gloo", rank=rank, world_size=world)
         else:
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", dev))
-    else:
+    elif torch is not None:
         torch.cuda.set_device(0)
     g = flbamd_loader.load()
     g.init(dev if world > 1 else 0)
@@ -1246,6 +1292,9 @@ def main():
         step()
 
     def sync_all():
+        if torch is None:
+            assert L.flbgpu_sync() == 0, g.last_error()
+            return
         torch.cuda.synchronize()
         if dist is not None:
             dist.barrier()
@@ -1269,20 +1318,24 @@ def main():
     fused = "k_pg_emit" in prof
     # the fused output of the last timed step, copied out before anything reuses the filters' device buffers
     fused_host = None
-    if rank == 0:
+    if rank == 0 and (args.full or args.dump_outputs):
         import numpy as np
         kb = np.empty(int(o2.bytes), dtype=np.uint8)
         L.flbgpu_memcpy_d2h(kb.ctypes.data, o2.data, int(o2.bytes))
         koff = np.empty(n + 1, dtype=np.uint64)
         L.flbgpu_memcpy_d2h(koff.ctypes.data, o2.row_off, koff.nbytes)
         fused_host = (kb, koff)
-    # the parsed chunk itself, for the side measurements below (one unfused filter_parser run, untimed)
-    r1, o1 = fparser.filter_dev(chunk)
-    assert r1 == g.MODIFIED and int(o1.bytes) == parsed_bytes, (g.last_error(), int(o1.bytes), parsed_bytes)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, kb, koff, n, kept_records)
+    # the parsed chunk itself, for the checks and side measurements below (one unfused filter_parser run, untimed)
+    o1 = None
+    if args.full:
+        r1, o1 = fparser.filter_dev(chunk)
+        assert r1 == g.MODIFIED and int(o1.bytes) == parsed_bytes, (g.last_error(), int(o1.bytes), parsed_bytes)
     # BASELINE configs[1] proper -- filter_parser ALONE (the headline adds configs[0]'s grep behind it): every record parsed and
     # written back, SURVEY 8(d)'s 277 + 275 B/record
     parser_only = None
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(3):
@@ -1308,7 +1361,7 @@ def main():
     #      unfused filter_parser -> filter_grep kernels write for the same chunk; (b) 4 000 consecutive-in-blocks rows against the
     #      oracle: the output rows of four blocks of 1 000 input records (start, two inside, end) byte for byte
     verify = None
-    if rank == 0:
+    if rank == 0 and args.full:
         try:
             verify = verify_timed_output(g, L, data, off, n, fused_host, o1, fgrep, args, cpu)
         except Exception as e:
@@ -1316,7 +1369,7 @@ def main():
 
     # ---- side measurements (never part of `value`): the other rows of the hot-path scope table
     secondary = None
-    if not args.no_secondary:
+    if args.full and not args.no_secondary:
         try:
             secondary = measure_secondary(g, torch, dist, rank, world, o1, n, args, raw_chunk=chunk, shared_gpu=shared_gpu)
             if parser_only is not None:
@@ -1357,7 +1410,7 @@ def main():
         live = None
         # --pmc, or by itself when the committed summary was recorded from other kernel sources than this tree's (an edit since the
         # last profile): the traffic of THIS build is measured now rather than left null (--no-pmc keeps it null)
-        auto_pmc = traffic is None and not args.no_pmc and not args.pmc and world == 1
+        auto_pmc = args.full and traffic is None and not args.no_pmc and not args.pmc and world == 1
         if (args.pmc or auto_pmc) and world == 1:
             # the same step twice more under rocprofv3 (children), after this process has finished its own timing
             live, live_src = pmc_pass(n, min(args.steps, 3) if auto_pmc else args.steps, args.warmup, timeout=200 if auto_pmc else 900)
@@ -1399,7 +1452,7 @@ def main():
         "metric": "log records/sec (256B apache-combined lines) through parser+grep",
         "value": round(value, 1), "unit": "records/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+        "vs_baseline": None, "dtype": "u8", "data": "synthetic", "full": bool(args.full),
         "config": {"workload": "filter_parser(conf/parsers.conf apache2, Key_Name log) -> filter_grep(Regex code ^5\\d\\d$) "
                                "on %d x 256B apache-combined lines per GPU (277B V2 events), flb_filter_do on device, %s" % (n, "fused pair: one pass over the chunk (event decode, capture program, time, rules on the capture spans), only the kept records written" if fused else "unfused"),
                    "records_per_gpu": n, "in_bytes": in_bytes, "parsed_bytes": parsed_bytes, "kept_records": int(kept_records),

