@@ -63,6 +63,11 @@ def lib():
     L.flbgpu_filter_parser_create.argtypes = [c_char_p, c_int, c_int, c_int, POINTER(c_void_p)]
     L.flbgpu_filter_grep_create.restype = c_void_p
     L.flbgpu_filter_grep_create.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p]
+    L.flbgpu_filter_modify_create.restype = c_void_p
+    L.flbgpu_filter_modify_create.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p)]
+    L.flbgpu_modify_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
+    L.flbgpu_modify_overread.restype = c_uint64
+    L.flbgpu_modify_overread.argtypes = [c_void_p]
     L.flbgpu_filter_destroy.argtypes = [c_void_p]
     L.flbgpu_filter_run.argtypes = [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]
     L.flbgpu_filter_run_dev.argtypes = [c_void_p, POINTER(DevChunk), POINTER(DevChunk), c_void_p]
@@ -297,6 +302,35 @@ class FilterGrep(_Filter):
         self.h = lib().flbgpu_filter_grep_create(n, kinds, vals, _b(logical_op))
         if not self.h:
             raise ValueError("flbgpu_filter_grep_create: " + last_error())
+
+
+def _props(props):
+    n = len(props)
+    names = (c_char_p * max(n, 1))(*[_b(k) for k, _ in props])
+    vals = (c_char_p * max(n, 1))(*[_b(v) for _, v in props])
+    return n, names, vals
+
+
+class FilterModify(_Filter):
+    """filter_modify: props = [(name, value), ...] in configuration order, e.g. [("Condition", "Key_exists agent"),
+    ("Rename", "host client")] (plugins/filter_modify/modify.c:141-519)"""
+
+    def __init__(self, props):
+        self.h = lib().flbgpu_filter_modify_create(*_props(props))
+        if not self.h:
+            raise ValueError("flbgpu_filter_modify_create: " + last_error())
+
+    def overread(self):
+        """records whose prefix test would have read past the record in the reference (flb_gpu.h flbgpu_modify_overread)"""
+        return int(lib().flbgpu_modify_overread(self.h))
+
+
+def modify_parse_check(props):
+    """the program setup() builds from props as one line of text (host only); raises ValueError where create refuses"""
+    buf = ctypes.create_string_buffer(1 << 16)
+    if lib().flbgpu_modify_parse_check(*_props(props), buf, len(buf)) != 0:
+        raise ValueError(last_error())
+    return buf.value.decode()
 
 
 JSON_FORMAT = {"json": 1, "stream": 2, "lines": 3}                                        # flb_pack_to_json_format_type

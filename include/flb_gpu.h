@@ -118,6 +118,25 @@ flbgpu_filter *flbgpu_filter_parser_create(const char *key_name, int reserve_dat
 flbgpu_filter *flbgpu_filter_grep_create(int nrules, const char *const *kinds, const char *const *values,
                                          const char *logical_op);
 
+/* ---- filter_modify: replaces cb_modify_init / cb_modify_filter / cb_modify_exit --------------------
+ * plugins/filter_modify/modify.c:141-519 (setup), 523-1457 (conditions, rules, one record), 1486-1578 (one call).
+ * (names[i], values[i]) are the instance's properties in configuration order, e.g. {"Condition", "Key_value_matches code ^5"},
+ * {"Rename", "host client"}.  Each value is split as flb_utils_split_quoted(val, ' ', 3) does; a rule of three tokens is a Rename of
+ * the first to the last (modify.h:28-29).  Every rule's key and value must compile as flb_regex_create would (:478-507); a pattern
+ * that runs per record (condition a of A_key_matches / No_key_matches / Matching_keys_*, b of Key_value_*match* / Matching_keys_*,
+ * the key of Remove_regex) must be a regular expression.  Refused, NULL + last_error: what cb_init refuses, a Condition of one
+ * token, Hard_copy of a key onto itself, a condition pattern Onigmo refuses (cb_init takes it and the first record dereferences the
+ * NULL regex, :321-341), an unterminated quote, more than 64 rules or 32 conditions.  Runs through flbgpu_filter_run[_dev],
+ * flbgpu_filter_chain_run[_dev], flbgpu_filter_last_counts and flbgpu_filter_destroy. */
+flbgpu_filter *flbgpu_filter_modify_create(int nprops, const char *const *names, const char *const *values);
+/* host only, no device: the program setup() builds from the same properties as one line of text (for CPU tests, like
+ * flbgpu_sp_parse_check); 0, or -1 + last_error where flbgpu_filter_modify_create refuses */
+int flbgpu_modify_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap);
+/* the counted difference of filter_modify's prefix test (Remove_wildcard, Move_to_start, Move_to_end: strncmp, :599-616): records
+ * whose compare would have read past the record (or past the re-packed map) in the reference, since the filter was created; the
+ * device answers "no match" there */
+uint64_t flbgpu_modify_overread(flbgpu_filter *f);
+
 /* ---- filter_log_to_metrics: replaces cb_log_to_metrics_init / cb_log_to_metrics_filter -----------
  * plugins/filter_log_to_metrics/log_to_metrics.c:655-968,970-1156.  (keys[i], values[i]) are the
  * instance's properties in configuration order; the ones read are regex / exclude (set_rules
