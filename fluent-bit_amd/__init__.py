@@ -68,6 +68,9 @@ def lib():
     L.flbgpu_modify_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
     L.flbgpu_modify_overread.restype = c_uint64
     L.flbgpu_modify_overread.argtypes = [c_void_p]
+    L.flbgpu_filter_record_modifier_create.restype = c_void_p
+    L.flbgpu_filter_record_modifier_create.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p)]
+    L.flbgpu_record_modifier_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
     L.flbgpu_filter_destroy.argtypes = [c_void_p]
     L.flbgpu_filter_run.argtypes = [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]
     L.flbgpu_filter_run_dev.argtypes = [c_void_p, POINTER(DevChunk), POINTER(DevChunk), c_void_p]
@@ -329,6 +332,25 @@ def modify_parse_check(props):
     """the program setup() builds from props as one line of text (host only); raises ValueError where create refuses"""
     buf = ctypes.create_string_buffer(1 << 16)
     if lib().flbgpu_modify_parse_check(*_props(props), buf, len(buf)) != 0:
+        raise ValueError(last_error())
+    return buf.value.decode()
+
+
+class FilterRecordModifier(_Filter):
+    """filter_record_modifier: props = [(name, value), ...] in configuration order, e.g. [("Record", "hostname h"),
+    ("Remove_key", "agent")] (plugins/filter_record_modifier/filter_modifier.c:69-155).  filter() may answer -1: a body map of more
+    than 65535 entries (:369-377)"""
+
+    def __init__(self, props):
+        self.h = lib().flbgpu_filter_record_modifier_create(*_props(props))
+        if not self.h:
+            raise ValueError("flbgpu_filter_record_modifier_create: " + last_error())
+
+
+def record_modifier_parse_check(props):
+    """the program configure() builds from props as one line of text (host only); raises ValueError where create refuses"""
+    buf = ctypes.create_string_buffer(1 << 17)
+    if lib().flbgpu_record_modifier_parse_check(*_props(props), buf, len(buf)) != 0:
         raise ValueError(last_error())
     return buf.value.decode()
 

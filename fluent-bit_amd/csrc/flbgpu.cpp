@@ -2378,6 +2378,7 @@ static int run_any_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_
         if (ok && ret == FLBGPU_FILTER_MODIFIED && out) memset(out, 0, sizeof(*out));   // discard_logs: every record dropped
     }
     else if (f->kind == F_MODIFY) ok = run_modify_dev(f, in, out, st, &ret, garbage);
+    else if (f->kind == F_RECMOD) ok = run_recmod_dev(f, in, out, st, &ret, garbage);
     else ok = f->kind == F_PARSER ? run_parser_dev(f, in, out, st, &ret) : run_grep_dev(f, in, out, st, &ret, garbage);
     if (!ok) return FLBGPU_FILTER_NOTOUCH;      // errors degrade to NOTOUCH (SURVEY 8b "Errors")
     return ret;
@@ -2557,6 +2558,8 @@ static int chain_dev(flbgpu_filter *const *filters, int n, const flbgpu_dev_chun
             stats[i].out_records = ret == FLBGPU_FILTER_MODIFIED ? filters[i]->last_out : filters[i]->last_in;
             stats[i].out_bytes = ret == FLBGPU_FILTER_MODIFIED ? o.bytes : cur.bytes;
         }
+        // (flb_filter_do treats every answer but MODIFIED alike; a single filter's own error code -- record_modifier's -1 -- goes to the caller)
+        if (ret < 0 && n == 1) { *out = cur; return ret; }
         if (ret != FLBGPU_FILTER_MODIFIED) continue;
         modified = true;
         cur = o;
@@ -2916,7 +2919,8 @@ extern "C" int flbgpu_filter_chain_run(flbgpu_filter *const *filters, int nfilte
     memset(&out, 0, sizeof(out));
     {
         PhaseScope ph(HP_CHAIN);
-        if (chain_dev(filters, nfilters, &in, &out, garbage, stats) != FLBGPU_FILTER_MODIFIED) return FLBGPU_FILTER_NOTOUCH;
+        const int cr = chain_dev(filters, nfilters, &in, &out, garbage, stats);
+        if (cr != FLBGPU_FILTER_MODIFIED) return cr < 0 ? cr : FLBGPU_FILTER_NOTOUCH;
     }
     if (out.bytes == 0) { *out_buf = NULL; *out_size = 0; return FLBGPU_FILTER_MODIFIED; }
     void *hb;

@@ -1,0 +1,223 @@
+// recmod_kernels.inc -- filter_record_modifier (plugins/filter_record_modifier/filter_modifier.c:213-279, 298-486): a lane per
+// record.  One walk over the body's top-level entries decides each key against the key table in LDS (make_bool_map) and adds up the
+// canonical size of what stays; the body's order never changes and nothing is inserted between entries, so no entry list is kept.
+// Two launches around the shared scan: the size pass writes every row's output length, the emit pass walks the body
+// again, decides again (the table is in LDS, the key bytes are in the cache lines it copies anyway) and copies runs of adjacent kept
+// entries whose encoding is already canonical as one span.  Included inside namespace flbgpu after kdev.inc.
+
+struct RmTable {
+    const LDS_AS uint32_t *w;       // the table's words in LDS
+    int nkeys;
+    int list;
+};
+
+// ASCII upper case -> lower case in the four bytes of a word (strncasecmp in the C locale; bytes >= 0x80 stay)
+DEV uint32_t rm_fold4(uint32_t x) {
+    const uint32_t h = x & 0x7f7f7f7fu;
+    const uint32_t ge_a = h + 0x3f3f3f3fu;          // bit 7: low seven bits >= 'A'
+    const uint32_t gt_z = h + 0x25252525u;          // bit 7: low seven bits >  'Z'
+    const uint32_t m = ge_a & ~gt_z & ~x & 0x80808080u;
+    return x | (m >> 2);
+}
+DEV uint32_t rm_fold1(uint32_t c) { return (c - 'A') < 26u ? c | 0x20u : c; }
+
+// make_bool_map's inner loop (:248-270) for one STR / BIN key: does an entry of the table match?  An exact entry needs the same
+// length, a prefix entry a key at least as long; then `length` bytes are compared without case -- never more than the key holds.
+DEV bool rm_match(const RmTable &tb, const uint8_t *key, uint32_t klen) {
+    for (int i = 0; i < tb.nkeys; i++) {
+        const uint32_t lw = tb.w[2 * i];
+        const uint32_t L = lw & ~RECMOD_PREFIX;
+        if ((lw & RECMOD_PREFIX) ? klen < L : klen != L) continue;
+        const LDS_AS uint32_t *e = tb.w + (tb.w[2 * i + 1] >> 2);
+        uint32_t j = 0;
+        bool eq = true;
+        for (; eq && j + 4 <= L; j += 4) eq = rm_fold4(ldu32(key + j)) == e[j >> 2];
+        if (eq && j < L) {
+            const uint32_t last = e[j >> 2];
+            for (uint32_t k = 0; eq && j + k < L; k++) eq = rm_fold1(ld8(key + j + k)) == ((last >> (8 * k)) & 0xffu);
+        }
+        if (eq) return true;
+    }
+    return false;
+}
+
+// is the entry with this key removed?  Only STR and BIN keys can match: with a remove list every other key stays, with an allow
+// list it goes (:260-274)
+DEV bool rm_removed(const RmTable &tb, const Tok &k) {
+    if (tb.list == RECMOD_NONE) return false;
+    const bool hit = (k.type == T_STR || k.type == T_BIN) && rm_match(tb, k.next, k.len);
+    return hit == (tb.list == RECMOD_REMOVE);
+}
+
+// one object at p (`open` containers around it): its end, nullptr when it is malformed, truncated or nested past the executor's limit.
+// csize grows by the size of msgpack_pack_object's re-pack; canon is cleared when a header is not the one the packer writes.
+DEV const uint8_t *rm_walk(const uint8_t *p, const uint8_t *end, uint32_t open, uint64_t &csize, bool &canon) {
+    const uint8_t *p0 = p;
+    uint64_t remaining = 1;
+    uint32_t nopen = 0;
+    while (remaining > 0) {
+        Tok t = mp_tok(p, end);
+        if (t.type == T_BAD) return nullptr;
+        remaining--;
+        const uint32_t c = ld8(p);
+        const uint32_t raw = (uint32_t) (t.next - p);
+        uint32_t pay = 0;
+        CountSink h;
+        switch (t.type) {
+        case T_UINT: pk_uint(h, t.u); if (c >= 0xd0 && c <= 0xd3) canon = false; break;      // a signed header on a value >= 0
+        case T_NINT: pk_int(h, (int64_t) t.u); break;
+        case T_STR: pk_str_hdr(h, t.len); pay = t.len; break;
+        case T_BIN: pk_bin_hdr(h, t.len); pay = t.len; break;
+        case T_EXT: pk_ext_hdr(h, t.len, 0); pay = t.len; break;
+        case T_ARRAY: pk_array_hdr(h, t.len); remaining += t.len; nopen++; break;
+        case T_MAP: pk_map_hdr(h, t.len); remaining += 2ull * t.len; nopen++; break;
+        default: h.n = raw; break;                                                          // nil, bool, float: one encoding
+        }
+        if ((uint32_t) h.n != raw) canon = false;
+        csize += h.n + pay;
+        p = t.next + pay;
+    }
+    if (open + nopen > MP_MAX_OPEN && !mp_depth_ok(p0, end, open)) return nullptr;
+    return p;
+}
+
+// the body is a dynamic field of the reference's encoder: its map header is always map32 (flb_mp_map_header_init, src/flb_mp.c:591-603)
+constexpr uint32_t RM_MAP_HDR = 5;
+
+struct RmRow {
+    bool bad, decoded, wide, lost;      // decoder error / a record the callback saw / more than 65535 entries / a key was removed
+    uint64_t len;                       // output bytes (0: nothing emitted)
+};
+
+// the time the encoder writes: flb_log_event_encoder_set_timestamp refuses a time outside the EventTime range, its answer is
+// overwritten (:414-417) and the record goes out with the zero time begin_record left
+DEV void rm_time(const Event &ev, uint32_t &sec, uint32_t &nsec) {
+    const bool ok = ev.sec >= 0 && (uint64_t) ev.sec <= 0xffffffffull && ev.nsec >= 0 && ev.nsec < 1000000000LL;
+    sec = ok ? (uint32_t) ev.sec : 0;
+    nsec = ok ? (uint32_t) ev.nsec : 0;
+}
+
+DEV void rm_copy(ByteSink &bs, const uint8_t *src, uint64_t len) {
+    while (len > 0x40000000ull) { bs.copy(src, 0x40000000u); src += 0x40000000ull; len -= 0x40000000ull; }
+    bs.copy(src, (uint32_t) len);
+}
+
+// size pass: one record of cb_modifier_filter's loop (:351-463)
+DEV RmRow rm_size(const RecmodArgs &a, const RmTable &tb, uint64_t r) {
+    RmRow w;
+    w.bad = false; w.decoded = false; w.wide = false; w.lost = false; w.len = 0;
+    const uint8_t *rec = a.data + a.row_off[r], *end = a.data + a.row_off[r + 1];
+    if (rec == end) return w;                                         // a record an earlier filter dropped
+    Event ev = decode_event(rec, end, true);
+    if (ev.flags & RF_BAD) { w.bad = true; return w; }
+    Tok bm = mp_tok(ev.body, end);
+    uint64_t size = 0;
+    uint32_t kept = 0;
+    bool canon = true;
+    const uint8_t *p = bm.next;
+    for (uint32_t i = 0; i < bm.len; i++) {
+        Tok k = mp_tok(p, end);
+        uint64_t es = 0;
+        p = rm_walk(p, end, 2, es, canon);
+        if (p) p = rm_walk(p, end, 2, es, canon);
+        if (!p) { w.bad = true; return w; }
+        if (!rm_removed(tb, k)) { kept++; size += es; }
+    }
+    if (p != end) { w.bad = true; return w; }                         // the row is one event and nothing else
+    if (ev.flags & RF_SKIP) return w;                                 // group markers: skipped by the decoder
+    w.decoded = true;
+    if (bm.len > 65535u) { w.wide = true; return w; }                 // BOOL_MAP_LIMIT (:369-377)
+    w.lost = kept != bm.len;
+    if (kept + a.nrec == 0) return w;                                 // (:408-410)
+    CountSink cs;
+    cs.n = 12 + RM_MAP_HDR;
+    if (ev.meta) mp_canon(ev.meta, ev.meta_end, cs); else cs.n += 1;
+    w.len = cs.n + size + a.tail_len;
+    return w;
+}
+
+// emit pass: the record whose length the size pass wrote
+DEV void rm_emit(const RecmodArgs &a, const RmTable &tb, uint64_t r) {
+    const uint8_t *rec = a.data + a.row_off[r], *end = a.data + a.row_off[r + 1];
+    Event ev = decode_event(rec, end, true);
+    ByteSink bs(a.out + a.out_off[r]);
+    uint32_t sec, nsec;
+    rm_time(ev, sec, nsec);
+    bs.put32(0x00d79292u);
+    bs.put32(__builtin_bswap32(sec));
+    bs.put32(__builtin_bswap32(nsec));
+    if (ev.meta) mp_canon(ev.meta, ev.meta_end, bs); else bs.put(0x80);
+    uint8_t *hdr = bs.p;                                              // the count is known when the walk is done
+    bs.p += RM_MAP_HDR;
+    Tok bm = mp_tok(ev.body, end);
+    const uint8_t *p = bm.next, *span = nullptr;
+    uint32_t kept = 0;
+    for (uint32_t i = 0; i < bm.len; i++) {
+        const uint8_t *e0 = p;
+        Tok k = mp_tok(p, end);
+        uint64_t es = 0;
+        bool canon = true;
+        const uint8_t *v = rm_walk(p, end, 2, es, canon);
+        p = rm_walk(v, end, 2, es, canon);
+        const bool keep = !rm_removed(tb, k);
+        kept += keep ? 1u : 0u;
+        if (keep && canon) { if (!span) span = e0; continue; }
+        if (span) { rm_copy(bs, span, (uint64_t) (e0 - span)); span = nullptr; }
+        if (keep) { mp_canon(e0, end, bs, 2); mp_canon(v, end, bs, 2); }
+    }
+    if (span) rm_copy(bs, span, (uint64_t) (p - span));
+    if (a.tail_len) bs.copy(a.tail, a.tail_len);
+    ByteSink hs(hdr);
+    hs.put(0xdf);
+    hs.put32(__builtin_bswap32(kept + a.nrec));
+}
+
+template <bool EMIT>
+__global__ void __launch_bounds__(RECMOD_BLOCK) k_recmod(RecmodArgs a) {
+    LDS_AS uint32_t *lds = (LDS_AS uint32_t *) g_lds;
+    for (uint32_t i = threadIdx.x; i < a.table_bytes / 4; i += RECMOD_BLOCK) lds[i] = a.table[i];
+    __syncthreads();
+    RmTable tb{lds, a.nkeys, a.list};
+    const uint64_t gsz = (uint64_t) gridDim.x * RECMOD_BLOCK;
+    const uint32_t lane = threadIdx.x & 63u;
+    unsigned long long n_dec = 0, n_out = 0, n_lost = 0, n_big = 0;
+    // every wave walks in step (the trip count is the wave's, not the lane's): the ballots below see whole waves
+    for (uint64_t r0 = (uint64_t) blockIdx.x * RECMOD_BLOCK + (threadIdx.x & ~63u); r0 < a.n; r0 += gsz) {
+        const uint64_t r = r0 + lane;
+        const bool live = r < a.n;
+        if (EMIT) {
+            if (live && a.len[r]) rm_emit(a, tb, r);
+            continue;
+        }
+        RmRow w;
+        w.bad = false; w.decoded = false; w.wide = false; w.lost = false; w.len = 0;
+        if (live) {
+            w = rm_size(a, tb, r);
+            const bool big = w.len > 0xFFFFFFFFull;                    // a row the u32 length column cannot hold
+            if (big) { n_big++; w.len = 0; }
+            a.len[r] = (uint32_t) w.len;
+            if (w.bad) atomicMin(a.first_bad, (unsigned long long) r);
+            if (w.wide) atomicMin(a.first_wide, (unsigned long long) r);
+        }
+        // the call-level facts of a wave's 64 records: counted by one lane from the ballots
+        const unsigned long long b_dec = __ballot(w.decoded), b_out = __ballot(w.len != 0), b_lost = __ballot(w.lost);
+        if (lane == 0) { n_dec += __popcll(b_dec); n_out += __popcll(b_out); n_lost += __popcll(b_lost); }
+    }
+    if (!EMIT) {
+        // one atomic per wave and counter that is not zero
+        if (lane == 0) {
+            if (n_dec) atomicAdd(&a.counts[0], n_dec);
+            if (n_out) atomicAdd(&a.counts[1], n_out);
+            if (n_lost) atomicAdd(&a.counts[2], n_lost);
+        }
+        if (n_big) atomicAdd(&a.counts[3], n_big);
+    }
+}
+
+void launch_recmod(const RecmodArgs &a, bool emit, hipStream_t st) {
+    if (a.n == 0) return;
+    uint64_t blocks = (a.n + RECMOD_BLOCK - 1) / RECMOD_BLOCK;
+    if (blocks > 65536) blocks = 65536;
+    if (emit) hipLaunchKernelGGL(k_recmod<true>, dim3((unsigned) blocks), dim3(RECMOD_BLOCK), a.table_bytes, st, a);
+    else hipLaunchKernelGGL(k_recmod<false>, dim3((unsigned) blocks), dim3(RECMOD_BLOCK), a.table_bytes, st, a);
+}

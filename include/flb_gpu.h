@@ -137,6 +137,33 @@ int flbgpu_modify_parse_check(int nprops, const char *const *names, const char *
  * device answers "no match" there */
 uint64_t flbgpu_modify_overread(flbgpu_filter *f);
 
+/* ---- filter_record_modifier: replaces cb_modifier_init / cb_modifier_filter / cb_modifier_exit --------
+ * plugins/filter_record_modifier/filter_modifier.c:69-155 (configure, behind the config map of :499-529), 213-279 (make_bool_map),
+ * 298-486 (one call).  (names[i], values[i]) are the instance's properties in configuration order, names without case:
+ *   Record         KEY VALUE, split as flb_slist_split_tokens(list, val, 2) (src/flb_slist.c:107-217: blanks, "quoted tokens" with \",
+ *                  the rest of the line as a third entry).  Fewer than two tokens fail the config map's size check for SLIST_2
+ *                  (src/flb_config_map.c:32-59) and the filter does not start; more than two are skipped as configure() skips them
+ *                  (:96-101).  The pairs are appended to every emitted record as STR, STR.  An emitted record is 92 92 d7 00 <sec>
+ *                  <nsec>, the metadata as msgpack-c re-packs it, a map32 header (the encoder's dynamic field always writes one,
+ *                  src/flb_mp.c:591-603), the kept entries re-packed in their order, the Record pairs.
+ *   Remove_key     a top-level key to remove; Allowlist_key / Whitelist_key (an alias that joins the allowlist, :145-147): only these
+ *                  stay.  A trailing '*' makes the entry a prefix (dynamic_key, :56-59, :134-137), '*' alone the empty prefix, which
+ *                  matches every STR or BIN key.  Keys compare as strncasecmp does in the C locale (ASCII folded, :260-265); only STR
+ *                  and BIN keys can match.  Both list kinds in one instance are refused (:149-153).
+ * Refused although the reference accepts them, NULL + last_error: Uuid_key (its value is random per record), an empty key (the
+ * reference reads key[-1], :56 and :134), more than 64 Record entries, more than 64 key entries, key entries of more than 32768
+ * bytes together (the table sits in LDS), a property the config map does not know.
+ * One call (:298-486): a record that keeps no entry and gets no Record entry is dropped from the output; a decoder error ends the
+ * loop and the call answers with the records in front of it; MODIFIED needs a removed key or a Record entry somewhere AND a byte of
+ * output, everything else is NOTOUCH; a body map of more than 65535 entries makes the call answer -1 (:369-377), which
+ * flbgpu_filter_run[_dev] hand through (a chain treats it as NOTOUCH, as flb_filter_do does).  A time outside the EventTime range
+ * goes out as 0.0: the encoder's refusal is overwritten (:412-417).  Runs through flbgpu_filter_run[_dev],
+ * flbgpu_filter_chain_run[_dev], flbgpu_filter_last_counts (records decoded / records emitted) and flbgpu_filter_destroy. */
+flbgpu_filter *flbgpu_filter_record_modifier_create(int nprops, const char *const *names, const char *const *values);
+/* host only, no device: the program configure() builds from the same properties as one line of text --
+ * "<none|remove|allow>;K<e|p>,<hex key>;...;R<hex key>,<hex value>;..." -- 0, or -1 + last_error where create refuses */
+int flbgpu_record_modifier_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap);
+
 /* ---- filter_log_to_metrics: replaces cb_log_to_metrics_init / cb_log_to_metrics_filter -----------
  * plugins/filter_log_to_metrics/log_to_metrics.c:655-968,970-1156.  (keys[i], values[i]) are the
  * instance's properties in configuration order; the ones read are regex / exclude (set_rules
