@@ -102,6 +102,7 @@ def lib():
     L.flbgpu_l2m_set_sum_order.argtypes = [c_void_p, c_int]
     L.flbgpu_l2m_seq_sums.restype = c_int64
     L.flbgpu_l2m_seq_sums.argtypes = [c_void_p, c_uint64, POINTER(c_double)]
+    L.flbgpu_seqsum_dev.argtypes = [c_void_p, c_void_p, c_uint64, ctypes.c_uint32, c_void_p]
     L.flbgpu_host_phases.restype = ctypes.c_int
     L.flbgpu_host_phases.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int]
     L.flbgpu_filter_host_rules.restype = ctypes.c_int

@@ -8,7 +8,11 @@
 //      dictionary needs: a single pass for up to 256 series);
 //   2. a series whose values of this call are ALL integers, with the running sum an integer too and |sum| + sum of |values| below 2^53 --
 //      byte counts, milliseconds, status codes: what log metrics mostly are --, has only exact partial sums, so its fold is one integer
-//      sum: a parallel pass over the sorted values (a block per 2048, one atomic per block and series);
+//      sum: a parallel pass over the sorted values (a block per 2048, one atomic per block and series).  The sum of the magnitudes is
+//      a 64-bit integer that 4097 values of 2^52 - 1 already wrap round to a small one: a contribution that is 2^53 or more by itself,
+//      or that takes the series' total there (the atomic's return value tells: below 2^53 nothing has wrapped yet), marks the series
+//      like a value that is no integer does, in the block-reduced and in the per-element pass alike, so a wrapped total is never
+//      looked at.  A running sum of -0.0 is no integer either: -0.0 + -0.0 is -0.0, which an integer sum cannot say;
 //   3. the others: a lane folds a short run (<= 256 observations) by itself, a wave folds a long one -- 512 values at a time, the next 512
 //      on their way while these are added (the same integer test per 512, else v_readlane + v_add_f64 one after the other, eight cycles
 //      each: the reference's bits have that price).
@@ -38,7 +42,8 @@ __global__ void __launch_bounds__(256) k_ss_runs(const uint32_t *keys, uint64_t 
         if (i == n - 1 && k < nseries) end[k] = n;
     }
 }
-// per series: are this call's values all integers (nonint[s] stays 0), their sum and the sum of their magnitudes (64-bit integers)
+// per series: are this call's values all integers with a sum of magnitudes below 2^53 (nonint[s] stays 0), their sum and the sum of
+// their magnitudes (64-bit integers; both may have wrapped once nonint[s] is set)
 __global__ void __launch_bounds__(256) k_ss_ints(const uint32_t *keys, const uint64_t *vals, uint64_t n, uint32_t nseries, unsigned int *nonint, long long *isum,
                                                  unsigned long long *imag) {
     __shared__ long long sh_sum[4];
@@ -61,7 +66,11 @@ __global__ void __launch_bounds__(256) k_ss_ints(const uint32_t *keys, const uin
                 const uint32_t k = keys[i];                                     // (a block that holds the end of a run: its own atomics)
                 if (k < nseries) {
                     if (!ok) atomicOr(&nonint[k], 1u);
-                    else { atomicAdd((unsigned long long *) &isum[k], (unsigned long long) q); atomicAdd(&imag[k], (unsigned long long) (q < 0 ? -q : q)); }
+                    else {
+                        const unsigned long long m = (unsigned long long) (q < 0 ? -q : q);
+                        atomicAdd((unsigned long long *) &isum[k], (unsigned long long) q);
+                        if (atomicAdd(&imag[k], m) + m >= 9007199254740992ull) atomicOr(&nonint[k], 1u);      // (the first to cross sees it unwrapped)
+                    }
                 }
             }
         }
@@ -72,15 +81,17 @@ __global__ void __launch_bounds__(256) k_ss_ints(const uint32_t *keys, const uin
             __syncthreads();
             if (threadIdx.x == 0) {
                 const unsigned int b = sh_bad[0] | sh_bad[1] | sh_bad[2] | sh_bad[3];
-                if (b) atomicOr(&nonint[k0], 1u);
+                const unsigned long long m = sh_mag[0] + sh_mag[1] + sh_mag[2] + sh_mag[3];          // (2048 values below 2^52: below 2^63)
+                if (b || m >= 9007199254740992ull) atomicOr(&nonint[k0], 1u);
                 else {
                     atomicAdd((unsigned long long *) &isum[k0], (unsigned long long) (sh_sum[0] + sh_sum[1] + sh_sum[2] + sh_sum[3]));
-                    atomicAdd(&imag[k0], sh_mag[0] + sh_mag[1] + sh_mag[2] + sh_mag[3]);
+                    if (atomicAdd(&imag[k0], m) + m >= 9007199254740992ull) atomicOr(&nonint[k0], 1u);
                 }
             }
         }
     }
 }
+__device__ __forceinline__ bool ss_neg_zero(double a) { return __double_as_longlong(a) == (long long) 0x8000000000000000ull; }
 // a series of integers is done with one addition; short runs by a lane each; long ones are listed for the wave kernel
 __global__ void __launch_bounds__(256) k_ss_fold_small(const uint64_t *vals, const unsigned long long *start, const unsigned long long *end, uint32_t nseries,
                                                        double *seq, uint32_t *heavy, unsigned int *nheavy, const unsigned int *nonint, const long long *isum,
@@ -90,7 +101,7 @@ __global__ void __launch_bounds__(256) k_ss_fold_small(const uint64_t *vals, con
         if (e <= b) continue;
         {
             const double a0 = seq[s];
-            if (!nonint[s] && fabs(a0) < 4503599627370496.0 && a0 == floor(a0) && imag[s] < 4503599627370496ull) {
+            if (!nonint[s] && fabs(a0) < 4503599627370496.0 && a0 == floor(a0) && !ss_neg_zero(a0) && imag[s] < 4503599627370496ull) {
                 const long long q0 = (long long) a0;
                 if ((unsigned long long) (q0 < 0 ? -q0 : q0) + imag[s] < 9007199254740992ull) { seq[s] = (double) (q0 + isum[s]); continue; }      // every partial sum exact
             }
@@ -138,7 +149,7 @@ __global__ void __launch_bounds__(64) k_ss_fold_heavy(const uint64_t *vals, cons
                 const long long q = ints ? (long long) v[u] : 0;
                 mine += q; mag += q < 0 ? -q : q;
             }
-            const bool acc_int = fabs(acc) < 4503599627370496.0 && acc == floor(acc);
+            const bool acc_int = fabs(acc) < 4503599627370496.0 && acc == floor(acc) && !ss_neg_zero(acc);
             if (__ballot(ints) == ~0ull && acc_int) {
                 const long long total_mag = ss_wave_sum(mag), a0 = (long long) acc;
                 if ((a0 < 0 ? -a0 : a0) + total_mag < 9007199254740992ll) {

@@ -208,9 +208,14 @@ int flbgpu_l2m_finalize_row(int mode, int nbuckets, const uint64_t *row, double 
  * to that process for ANY number of ranks.  flbgpu_l2m_chain_sums: the last flush's sums in the order of its output.  The three steps
  * of the chain are entry points of their own for a merge that runs over another transport (the Python helper over torch.distributed):
  * chain_begin fills `sums` with what the last flush ended on for the union of the label tuples (key_off / keys as flbgpu_l2m_export
- * writes them), seq_replay is this rank's turn (in / out), chain_end keeps the final sums on every rank. */
+ * writes them), seq_replay is this rank's turn (in / out), chain_end keeps the final sums on every rank.
+ * flbgpu_seqsum_dev (a test aid, no filter behind it): the kernels of that sum on host columns the caller supplies -- observation i
+ * belongs to series sid[i] (an id >= nseries is no observation) and has the binary64 bits val_bits[i]; seq_inout[nseries] holds the
+ * start sums and gets the results.  The columns are copied to the device, the kernels run, the sums are copied back; 0, or -1 with
+ * flbgpu_last_error (there is no host path behind it).  n == 0 or nseries == 0 leaves seq_inout alone and returns 0. */
 int flbgpu_l2m_set_sum_order(flbgpu_filter *f, int reference);
 int64_t flbgpu_l2m_seq_sums(flbgpu_filter *f, uint64_t max_series, double *sums);
+int flbgpu_seqsum_dev(const uint32_t *sid, const uint64_t *val_bits, uint64_t n, uint32_t nseries, double *seq_inout);
 int flbgpu_l2m_chain_begin(flbgpu_filter *f, uint64_t n_keys, const uint64_t *key_off, const char *keys, double *sums);
 int flbgpu_l2m_seq_replay(flbgpu_filter *f, uint64_t n_keys, const uint64_t *key_off, const char *keys, double *sums);
 int flbgpu_l2m_chain_end(flbgpu_filter *f, uint64_t n_keys, const uint64_t *key_off, const char *keys, const double *sums);

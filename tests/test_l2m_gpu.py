@@ -194,6 +194,7 @@ def test_histogram_exact_sum(g):
     data = b"".join(recs)
     n, off, _ = g.index_host(data)
     cut = [0, int(off[n // 3]), int(off[2 * n // 3]), len(data)]
+    # (sum_mode "none": this test is about sum_exact; the sequential sum on this value mix is tests/test_seqsum_gpu.py's)
     check(g, "histogram", [("label_field", "k")], [data[cut[i]:cut[i + 1]] for i in range(3)], value_field="v", exact_sums=exact,
           sum_mode="none")
     # non-finite observations
