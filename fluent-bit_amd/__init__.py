@@ -71,6 +71,11 @@ def lib():
     L.flbgpu_filter_record_modifier_create.restype = c_void_p
     L.flbgpu_filter_record_modifier_create.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p)]
     L.flbgpu_record_modifier_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
+    L.flbgpu_filter_nest_create.restype = c_void_p
+    L.flbgpu_filter_nest_create.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p)]
+    L.flbgpu_nest_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
+    L.flbgpu_nest_counters.restype = None
+    L.flbgpu_nest_counters.argtypes = [c_void_p, POINTER(c_uint64)]
     L.flbgpu_filter_destroy.argtypes = [c_void_p]
     L.flbgpu_filter_run.argtypes = [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]
     L.flbgpu_filter_run_dev.argtypes = [c_void_p, POINTER(DevChunk), POINTER(DevChunk), c_void_p]
@@ -352,6 +357,31 @@ def record_modifier_parse_check(props):
     """the program configure() builds from props as one line of text (host only); raises ValueError where create refuses"""
     buf = ctypes.create_string_buffer(1 << 17)
     if lib().flbgpu_record_modifier_parse_check(*_props(props), buf, len(buf)) != 0:
+        raise ValueError(last_error())
+    return buf.value.decode()
+
+
+class FilterNest(_Filter):
+    """filter_nest: props = [(name, value), ...] in configuration order, e.g. [("Operation", "lift"), ("Nested_under", "kubernetes"),
+    ("Add_prefix", "k8s_")] (plugins/filter_nest/nest.c:57-175)"""
+
+    def __init__(self, props):
+        self.h = lib().flbgpu_filter_nest_create(*_props(props))
+        if not self.h:
+            raise ValueError("flbgpu_filter_nest_create: " + last_error())
+
+    def counters(self):
+        """(records built again, compares past the record's end, undefined records, rows over 4 GB) since the filter was created
+        (flb_gpu.h flbgpu_nest_counters)"""
+        o = (c_uint64 * 4)()
+        lib().flbgpu_nest_counters(self.h, o)
+        return tuple(int(x) for x in o)
+
+
+def nest_parse_check(props):
+    """the program configure() builds from props as one line of text (host only); raises ValueError where create refuses"""
+    buf = ctypes.create_string_buffer(1 << 17)
+    if lib().flbgpu_nest_parse_check(*_props(props), buf, len(buf)) != 0:
         raise ValueError(last_error())
     return buf.value.decode()
 

@@ -139,12 +139,14 @@ uint64_t l2m_limbs_bits(const uint64_t *limbs, uint64_t n_nan, uint64_t n_pinf, 
 struct KernelProf { const char *name; double ms = 0; uint64_t launches = 0; };
 struct ProfPending { const char *name; hipEvent_t e0, e1; };
 
-enum { F_PARSER = 1, F_GREP = 2, F_L2M = 3, F_JSONFMT = 4, F_MODIFY = 5, F_RECMOD = 6 };
+enum { F_PARSER = 1, F_GREP = 2, F_L2M = 3, F_JSONFMT = 4, F_MODIFY = 5, F_RECMOD = 6, F_NEST = 7 };
 
 struct ModState;                 // filter_modify's program and buffers (modify.cpp)
 void mod_state_destroy(ModState *);
 struct RecmodState;              // filter_record_modifier's program and buffers (recmod.cpp)
 void recmod_state_destroy(RecmodState *);
+struct NestState;                // filter_nest's program and buffers (nest.cpp)
+void nest_state_destroy(NestState *);
 
 struct flbgpu_filter {
     int kind = 0;
@@ -212,6 +214,8 @@ struct flbgpu_filter {
     ModState *mod = nullptr;
     // filter_record_modifier
     RecmodState *recmod = nullptr;
+    // filter_nest
+    NestState *nest = nullptr;
     bool host_list = false;                     // filter_parser: a list of several parsers with host parsers in it (flbgpu.cpp host_list_rx)
     flbgpu::DevBuf d_hres[flbgpu::MAX_HOST_PARSERS];   // their answers for the chunk at hand
     // msgpack -> JSON output formatter (packfmt.cpp)
@@ -234,6 +238,7 @@ struct flbgpu_filter {
         if (l2m) l2m_state_destroy(l2m);
         mod_state_destroy(mod);
         recmod_state_destroy(recmod);
+        nest_state_destroy(nest);
         for (auto *b : rule_blobs) delete b;
         for (auto *b : host_rx) if (b) rx::bt_free(b);
         delete l2m_gate;
@@ -283,6 +288,8 @@ bool resolve_raw_chunk(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_
 bool run_modify_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
 // filter_record_modifier entry (recmod.cpp); *ret may be -1: a body map over the reference's 65535-entry limit
 bool run_recmod_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
+// filter_nest entry (nest.cpp)
+bool run_nest_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
 
 // filter_log_to_metrics entry used by flbgpu_filter_run / flbgpu_filter_run_dev
 bool run_l2m_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, hipStream_t st, int *ret);

@@ -1,16 +1,16 @@
-// kernels_recmod.hip -- filter_record_modifier, a lane per record (recmod_kernels.inc; shares kdev.inc with the other kernel units)
+// kernels_nest.hip -- filter_nest, a lane per record (nest_kernels.inc; shares kdev.inc with the other kernel units)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 #include <type_traits>
 #include "dev.hpp"
 #include "numconv.hpp"
-#include "recmod.hpp"
+#include "nest.hpp"
 
 namespace flbgpu {
 
 #include "kdev.inc"
 #include "canon_walk.inc"
-#include "recmod_kernels.inc"
+#include "nest_kernels.inc"
 
 }  // namespace flbgpu

@@ -3,7 +3,8 @@
 // canonical size of what stays; the body's order never changes and nothing is inserted between entries, so no entry list is kept.
 // Two launches around the shared scan: the size pass writes every row's output length, the emit pass walks the body
 // again, decides again (the table is in LDS, the key bytes are in the cache lines it copies anyway) and copies runs of adjacent kept
-// entries whose encoding is already canonical as one span.  Included inside namespace flbgpu after kdev.inc.
+// entries whose encoding is already canonical as one span.  Included inside namespace flbgpu after kdev.inc and
+// canon_walk.inc (rm_walk, RM_MAP_HDR, rm_copy).
 
 struct RmTable {
     const LDS_AS uint32_t *w;       // the table's words in LDS
@@ -49,41 +50,6 @@ DEV bool rm_removed(const RmTable &tb, const Tok &k) {
     return hit == (tb.list == RECMOD_REMOVE);
 }
 
-// one object at p (`open` containers around it): its end, nullptr when it is malformed, truncated or nested past the executor's limit.
-// csize grows by the size of msgpack_pack_object's re-pack; canon is cleared when a header is not the one the packer writes.
-DEV const uint8_t *rm_walk(const uint8_t *p, const uint8_t *end, uint32_t open, uint64_t &csize, bool &canon) {
-    const uint8_t *p0 = p;
-    uint64_t remaining = 1;
-    uint32_t nopen = 0;
-    while (remaining > 0) {
-        Tok t = mp_tok(p, end);
-        if (t.type == T_BAD) return nullptr;
-        remaining--;
-        const uint32_t c = ld8(p);
-        const uint32_t raw = (uint32_t) (t.next - p);
-        uint32_t pay = 0;
-        CountSink h;
-        switch (t.type) {
-        case T_UINT: pk_uint(h, t.u); if (c >= 0xd0 && c <= 0xd3) canon = false; break;      // a signed header on a value >= 0
-        case T_NINT: pk_int(h, (int64_t) t.u); break;
-        case T_STR: pk_str_hdr(h, t.len); pay = t.len; break;
-        case T_BIN: pk_bin_hdr(h, t.len); pay = t.len; break;
-        case T_EXT: pk_ext_hdr(h, t.len, 0); pay = t.len; break;
-        case T_ARRAY: pk_array_hdr(h, t.len); remaining += t.len; nopen++; break;
-        case T_MAP: pk_map_hdr(h, t.len); remaining += 2ull * t.len; nopen++; break;
-        default: h.n = raw; break;                                                          // nil, bool, float: one encoding
-        }
-        if ((uint32_t) h.n != raw) canon = false;
-        csize += h.n + pay;
-        p = t.next + pay;
-    }
-    if (open + nopen > MP_MAX_OPEN && !mp_depth_ok(p0, end, open)) return nullptr;
-    return p;
-}
-
-// the body is a dynamic field of the reference's encoder: its map header is always map32 (flb_mp_map_header_init, src/flb_mp.c:591-603)
-constexpr uint32_t RM_MAP_HDR = 5;
-
 struct RmRow {
     bool bad, decoded, wide, lost;      // decoder error / a record the callback saw / more than 65535 entries / a key was removed
     uint64_t len;                       // output bytes (0: nothing emitted)
@@ -95,11 +61,6 @@ DEV void rm_time(const Event &ev, uint32_t &sec, uint32_t &nsec) {
     const bool ok = ev.sec >= 0 && (uint64_t) ev.sec <= 0xffffffffull && ev.nsec >= 0 && ev.nsec < 1000000000LL;
     sec = ok ? (uint32_t) ev.sec : 0;
     nsec = ok ? (uint32_t) ev.nsec : 0;
-}
-
-DEV void rm_copy(ByteSink &bs, const uint8_t *src, uint64_t len) {
-    while (len > 0x40000000ull) { bs.copy(src, 0x40000000u); src += 0x40000000ull; len -= 0x40000000ull; }
-    bs.copy(src, (uint32_t) len);
 }
 
 // size pass: one record of cb_modifier_filter's loop (:351-463)

@@ -164,6 +164,46 @@ flbgpu_filter *flbgpu_filter_record_modifier_create(int nprops, const char *cons
  * "<none|remove|allow>;K<e|p>,<hex key>;...;R<hex key>,<hex value>;..." -- 0, or -1 + last_error where create refuses */
 int flbgpu_record_modifier_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap);
 
+/* ---- filter_nest: replaces cb_nest_init / cb_nest_filter / cb_nest_exit ------------------------------
+ * plugins/filter_nest/nest.c:57-175 (configure, behind the config map of :729-761), 298-345 (is_kv_to_nest), 353-397 (is_kv_to_lift),
+ * 473-533 (apply_lifting_rules), 535-606 (apply_nesting_rules), 631-717 (one call).  (names[i], values[i]) are the instance's
+ * properties in configuration order, names without case:
+ *   Operation      accepted when its first four bytes are "nest" or "lift" (strncmp(.., 4), with their case, :85-96: "nested" and
+ *                  "lifting" pass, "Nest" does not).
+ *   Wildcard       the only name that may repeat (FLB_CONFIG_MAP_MULT, :735-739): any other name set twice is refused, as the config
+ *                  map refuses it ("is set 2 times").  A trailing '*' makes the entry a prefix (key_is_dynamic, :115-121), '*' alone the empty prefix, which
+ *                  matches every STR or BIN key.  Only STR and BIN keys can match (:311-322).
+ *   Nest_under, Nested_under   both set the one key, for either operation; when both names are given the later of the two
+ *                  wins (:127-134).  The same name twice is refused like any other repeat.
+ *   Add_prefix, Remove_prefix  both set the one prefix; giving both is refused (:156-159).  The prefix applies to nest as to lift.
+ * Refused although the reference accepts them, NULL + last_error: a missing Operation (the reference reads a field malloc left as it
+ * was, :161-165), an empty Wildcard value (the reference reads key[-1], :115), more than 64 Wildcard entries, wildcards, key and
+ * prefix of more than 32768 bytes together (the table sits in LDS), a property the config map does not know -- Prefix_with among
+ * them, which configure() knows (:135-139) and the config map does not.
+ * One call (:631-717): every decoded record yields one output row.  A record no rule changes (no key matches a wildcard; no entry is
+ * the key with a map value) goes out as its own bytes, not re-packed (emit_raw_record, :685-690).  nest: 92 92 d7 00 <sec> <nsec>, the
+ * metadata as msgpack-c re-packs it, a map32 header (src/flb_mp.c:591-603), the entries that do not match re-packed in their order,
+ * the key as STR, a map32 header, the matching entries in their order.  lift: every entry whose STR or BIN key equals the key and
+ * whose value is a map is lifted (duplicates too); the others come first, then the contents of each lifted map.  A nested or lifted
+ * entry's key is written as STR whenever a prefix is configured: the prefix and the key (Add_prefix), the key without the prefix where
+ * it starts with it (Remove_prefix).  Keys compare as strncmp does: a prefix wildcard and Remove_prefix compare their own length, so
+ * the record's bytes behind a shorter key take part ({"a": 98} matches "ab*"); a compare that would need bytes past the record fails
+ * and is counted.  Two cases the reference leaves undefined go out as the record's own bytes and are counted: Remove_prefix matching
+ * a key shorter than the prefix (a negative length, :183-187), and a prefix with a lifted map that holds a key that is neither STR nor
+ * BIN (:438-443).  A record the rules would change is lost -- neither built nor sent raw -- when its time is outside the EventTime
+ * range (:506-511, :561-566) or, for nest, when no key was given (the encoder refuses the NULL string, :582-587); a lift without a
+ * key lifts the maps under the empty key.  A decoder error ends the loop and the call answers with the records in front of it;
+ * MODIFIED whenever a byte came out, else NOTOUCH (:698-711) -- a chunk in which nothing matched comes back MODIFIED with its own
+ * bytes.  Runs through flbgpu_filter_run[_dev], flbgpu_filter_chain_run[_dev], flbgpu_filter_last_counts (records decoded / records
+ * emitted) and flbgpu_filter_destroy. */
+flbgpu_filter *flbgpu_filter_nest_create(int nprops, const char *const *names, const char *const *values);
+/* host only, no device: the program configure() builds from the same properties as one line of text --
+ * "<nest|lift>;K<hex key|->;P<a|r|n>,<hex prefix>;W<e|p>,<hex wildcard>;..." -- 0, or -1 + last_error where create refuses */
+int flbgpu_nest_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap);
+/* since the filter was created: out[0] records built again, out[1] compares that would have read past the record (the device answers
+ * "no match" there), out[2] records the reference leaves undefined (sent as their own bytes), out[3] rows over 4 GB (nothing emitted) */
+void flbgpu_nest_counters(flbgpu_filter *f, uint64_t out[4]);
+
 /* ---- filter_log_to_metrics: replaces cb_log_to_metrics_init / cb_log_to_metrics_filter -----------
  * plugins/filter_log_to_metrics/log_to_metrics.c:655-968,970-1156.  (keys[i], values[i]) are the
  * instance's properties in configuration order; the ones read are regex / exclude (set_rules
