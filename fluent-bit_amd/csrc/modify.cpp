@@ -136,8 +136,9 @@ bool cond_accessor(const std::string &a, MItem &it, std::string &why) {
 
 const char *const RULE_NAMES1[] = {"remove", "remove_wildcard", "remove_regex", "move_to_start", "move_to_end"};
 const int RULE_TYPES1[] = {MR_REMOVE, MR_REMOVE_WILDCARD, MR_REMOVE_REGEX, MR_MOVE_TO_START, MR_MOVE_TO_END};
-const char *const RULE_NAMES2[] = {"rename", "hard_rename", "add", "add_if_not_present", "set", "copy", "hard_copy"};
-const int RULE_TYPES2[] = {MR_RENAME, MR_HARD_RENAME, MR_ADD, MR_ADD, MR_SET, MR_COPY, MR_HARD_COPY};
+// (setup() also knows "add_if_not_present" (:447-452), but the config map (:1589-1655) does not: the filter refuses it before setup() runs)
+const char *const RULE_NAMES2[] = {"rename", "hard_rename", "add", "set", "copy", "hard_copy"};
+const int RULE_TYPES2[] = {MR_RENAME, MR_HARD_RENAME, MR_ADD, MR_SET, MR_COPY, MR_HARD_COPY};
 const char *const COND_NAMES[] = {"key_exists", "key_does_not_exist", "a_key_matches", "no_key_matches", "key_value_equals",
                                   "key_value_does_not_equal", "key_value_matches", "key_value_does_not_match",
                                   "matching_keys_have_matching_values", "matching_keys_do_not_have_matching_values"};
@@ -183,7 +184,7 @@ bool parse_program(int nprops, const char *const *names, const char *const *valu
             it.k = tok.front(); it.v = tok.back();
             bool known = false;
             for (int t = 0; t < 5; t++) if (!strcasecmp(name.c_str(), RULE_NAMES1[t])) { known = true; if (tok.size() == 1) it.type = RULE_TYPES1[t]; }
-            for (int t = 0; t < 7; t++) if (!strcasecmp(name.c_str(), RULE_NAMES2[t])) { known = true; if (tok.size() == 2) it.type = RULE_TYPES2[t]; }
+            for (int t = 0; t < 6; t++) if (!strcasecmp(name.c_str(), RULE_NAMES2[t])) { known = true; if (tok.size() == 2) it.type = RULE_TYPES2[t]; }
             // three tokens: the rule type stays at calloc's 0, RENAME (modify.h:28-29), of the first token to the last
             if (known && tok.size() == 3) it.type = MR_RENAME;
             if (it.type < 0) { why = "Invalid operation " + name + " : " + val + " in configuration"; return false; }

@@ -12,6 +12,8 @@
  *        src/flb_processor.c:1407-1437 calls the plugin's cb_filter under pu->lock) / flb_processor_run on the whole file as one chunk.
  *        Prints {"ret", "out_bytes", "seconds", "units": [{"name", "records", "dropped", "added"}]} (the per-filter cmetrics the
  *        reference's test asserts at :354-366); the output chunk goes to <out.mp>.
+ *        A FILTER unit's property named `condition` (filter_modify's) is set on the unit's filter instance: the processor keeps
+ *        that name for a unit condition of its own and refuses a string there.
  *   lib [-e <plugin.so>]... [--parser ...]... [--metrics-tag T] [--batch N] <in.json> <out.bin> --filter <filter> [k=v]... [--filter ...]...
  *        the whole engine (flb_create / flb_start: event loop, in_lib -> flb_input_chunk_append_raw -> flb_filter_do -> router ->
  *        out_lib): every line of <in.json> ('[ts, {..}]') is pushed with flb_lib_push, the log chunks out_lib hands over
@@ -26,6 +28,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <strings.h>
 #include <stdint.h>
 #include <unistd.h>
 #include <time.h>
@@ -167,7 +170,12 @@ static int cmd_processor(int argc, char **argv)
         else if (pu && strchr(argv[i], '=')) {
             char *kv = strdup(argv[i]), *eq = strchr(kv, '=');
             *eq = 0;
-            if (flb_processor_unit_set_property_str(pu, kv, eq + 1) != 0) { fprintf(stderr, "property %s refused\n", argv[i]); return 3; }
+            /* the processor keeps the name `condition` for itself (src/flb_processor.c:1093-1096: a unit's condition must be a map); a
+             * FILTER unit's own property of that name (filter_modify's Condition) goes to the unit's filter instance, where every
+             * other property of the unit ends up as well (:1099-1102) */
+            if (pu->unit_type == FLB_PROCESSOR_UNIT_FILTER && !strcasecmp(kv, "condition")) ret = flb_filter_set_property(pu->ctx, kv, eq + 1);
+            else ret = flb_processor_unit_set_property_str(pu, kv, eq + 1);
+            if (ret != 0) { fprintf(stderr, "property %s refused\n", argv[i]); return 3; }
             free(kv);
         }
         else if (!in_path) in_path = argv[i];

@@ -9,7 +9,8 @@ import struct
 
 # ---------------------------------------------------------------- configuration
 RULES1 = {"remove": 4, "remove_wildcard": 5, "remove_regex": 6, "move_to_start": 9, "move_to_end": 10}
-RULES2 = {"rename": 0, "hard_rename": 1, "add": 2, "add_if_not_present": 2, "set": 3, "copy": 7, "hard_copy": 8}
+# (setup() also knows "add_if_not_present", :447-452, but the config map, :1589-1655, does not: the filter refuses it before setup() runs)
+RULES2 = {"rename": 0, "hard_rename": 1, "add": 2, "set": 3, "copy": 7, "hard_copy": 8}
 RENAME, HARD_RENAME, ADD, SET, REMOVE, REMOVE_WILDCARD, REMOVE_REGEX, COPY, HARD_COPY, MOVE_TO_START, MOVE_TO_END = range(11)
 CONDS = ["key_exists", "key_does_not_exist", "a_key_matches", "no_key_matches", "key_value_equals", "key_value_does_not_equal",
          "key_value_matches", "key_value_does_not_match", "matching_keys_have_matching_values",
@@ -608,7 +609,11 @@ def record(raw, conds, rules, stats):
     assert end == len(raw)
     ctx = Ctx(raw)
     m = body
-    if not all([cond(body, c) for c in conds]):
+    verdicts = [cond(body, c) for c in conds]
+    for c, v in zip(conds, verdicts):
+        key = "cond_true" if v else "cond_false"
+        stats.setdefault(key, {})[c[1]] = stats.setdefault(key, {}).get(c[1], 0) + 1
+    if not all(verdicts):
         return raw, False
     applied = False
     for r in rules:
@@ -616,6 +621,7 @@ def record(raw, conds, rules, stats):
         if e is None:
             continue
         applied = True
+        stats.setdefault("rule_applied", {})[r[1]] = stats.setdefault("rule_applied", {}).get(r[1], 0) + 1
         ctx.buf = canon(Obj("map", e, None, None))
         m = unpack(ctx.buf, 0)
     if ctx.overread:
@@ -623,6 +629,100 @@ def record(raw, conds, rules, stats):
     if not applied or sec > 0xffffffff or nsec < 0 or nsec >= 1000000000:
         return raw, False
     return b"\x92\x92\xd7\x00" + struct.pack(">II", sec, nsec) + (canon(meta) if meta is not None else b"\x80") + canon(m), True
+
+
+def clean_cut(buf, p):
+    """whether the bytes from p on, which hold no whole object, end where msgpack-c's executor has consumed all it was given: it takes
+    whole fields (a type byte, a length field, a payload) and stops in front of the first one that is cut short
+    (lib/msgpack-c/include/msgpack/unpack_template.h:242-247,439-447).  The decoder's offset then stands at the end of the buffer and
+    cb_modify_filter reads its INSUFFICIENT_DATA as a clean end (:1550-1553)"""
+    n, count = len(buf), []
+    while True:
+        if p >= n:
+            return True
+        c, q = buf[p], p + 1
+        k, lb, items = 0, 0, None
+        if c <= 0x7f or c >= 0xe0 or c in (0xc0, 0xc2, 0xc3):
+            pass
+        elif c == 0xc1:
+            return False
+        elif 0xa0 <= c <= 0xbf:
+            k = c & 31
+        elif 0x90 <= c <= 0x9f:
+            items = c & 15
+        elif 0x80 <= c <= 0x8f:
+            items = 2 * (c & 15)
+        elif c in (0xcc, 0xd0):
+            k = 1
+        elif c in (0xcd, 0xd1, 0xd4):
+            k = 2
+        elif c in (0xce, 0xd2, 0xca):
+            k = 4
+        elif c in (0xcf, 0xd3, 0xcb):
+            k = 8
+        elif c in (0xd5, 0xd6, 0xd7, 0xd8):
+            k = {0xd5: 3, 0xd6: 5, 0xd7: 9, 0xd8: 17}[c]
+        else:
+            lb = 1 if c in (0xc4, 0xc7, 0xd9) else (2 if c in (0xc5, 0xc8, 0xda, 0xdc, 0xde) else 4)
+            if n - q < lb:
+                return q == n
+            v = int.from_bytes(buf[q:q + lb], "big")
+            q += lb
+            if c in (0xdc, 0xdd):
+                items = v
+            elif c in (0xde, 0xdf):
+                items = 2 * v
+            else:
+                k = v + (1 if c in (0xc7, 0xc8, 0xc9) else 0)
+        if items is None and n - q < k:
+            return q == n
+        p = q + k
+        if items is not None:
+            if len(count) >= 32:
+                return False
+            if items > 0:
+                count.append(items)
+                continue
+        while True:
+            if not count:
+                return False                   # a whole object after all: it is malformed, not cut
+            count[-1] -= 1
+            if count[-1] > 0:
+                break
+            count.pop()
+
+
+def processor_output(buf):
+    """what the reference's processor hands on of the buffer a filter unit left (flb_mp_normalize_log_buffer_groups_msgpack,
+    src/flb_mp.c:80-230, called at src/flb_processor.c:1811-1825): the records its decoder takes up to the first error, without a
+    group start that is never closed, a group end that has no start and a group that holds no record.  tools/gen_modify_golden.py
+    records behind it, so a rebuilt record whose time is 0xffffffff s -- a group start to this decoder -- is not in the recording."""
+    ent, p = [], 0
+    while p < len(buf):
+        try:
+            end, skip, sec, *_ = decode_event(buf, p)
+        except Bad:
+            break
+        ent.append([p, end, (sec if skip else 0), True])
+        p = end
+    stack = []
+    for e in ent:
+        if e[2] == -1:
+            stack.append([e, False])
+        elif e[2] == -2:
+            if not stack:
+                e[3] = False
+                continue
+            start, content = stack.pop()
+            if not content:
+                start[3] = e[3] = False
+            elif stack:
+                stack[-1][1] = True
+        elif stack:
+            stack[-1][1] = True
+    for start, _ in stack:
+        start[3] = False
+    return b"".join(buf[a:b] for a, b, _, keep in ent if keep)
 
 
 class Model:
@@ -642,7 +742,7 @@ class Model:
             try:
                 end, skip, *_ = decode_event(data, p)
             except Bad:
-                bad = True
+                bad = not clean_cut(data, p)
                 break
             if skip:
                 p = end
@@ -651,6 +751,7 @@ class Model:
             o, m = record(bytes(data[p:end]), self.conds, self.rules, self.stats)
             out.append(o)
             mod += m
+            self.stats["rebuilt" if m else "raw"] = self.stats.get("rebuilt" if m else "raw", 0) + 1
             p = end
         self.n_in = n
         if mod == 0 or bad:

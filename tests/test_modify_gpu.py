@@ -1,9 +1,10 @@
 """filter_modify on the device (csrc/modify_kernels.inc through flbgpu_filter_modify_create) against the CPU model
-(tests/modify_model.py): output bytes, return value and record counts"""
+(tests/modify_model.py) and against the recorded answers of the real plugin (tests/golden/modify_ref_cases.json): output bytes,
+return value, record counts and the overread counter"""
+import base64
 import json
 import os
 import random
-import struct
 import sys
 
 import pytest
@@ -11,12 +12,14 @@ import pytest
 HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 import flbamd_loader
+import modify_chunks as mc
 import modify_model as mm
 import oracle_binding as ob
 import synth
 
 pytestmark = pytest.mark.gpu
 CASES = json.load(open(os.path.join(HERE, "golden", "modify_runtime_cases.json")))["cases"]
+REF_CASES = json.load(open(os.path.join(HERE, "golden", "modify_ref_cases.json")))["cases"]
 APACHE2 = (r'^(?<host>[^ ]*) [^ ]* (?<user>[^ ]*) \[(?<time>[^\]]*)\] "(?<method>\S+)(?: +(?<path>[^ ]*) +\S*)?" '
            r'(?<code>[^ ]*) (?<size>[^ ]*)(?: "(?<referer>[^\"]*)" "(?<agent>.*)")?$')
 TIME_FMT = "%d/%b/%Y:%H:%M:%S %z"
@@ -59,86 +62,153 @@ def test_runtime_cases(g, case):
     same(g, [tuple(p) for p in case["props"]], data)
 
 
-KEYS = [b"a", b"ab", b"abc", b"abcd", b"k", b"k1", b"k2", b"log", b"re", b"ref", b"referer", b"x", b"", b"true", b"A3"]
+@pytest.mark.parametrize("case", REF_CASES, ids=[c["name"] for c in REF_CASES])
+def test_fixture_cases(g, case):
+    props = [tuple(p) for p in case["props"]]
+    if case.get("refused"):
+        with pytest.raises(ValueError):
+            g.FilterModify(props)
+        return
+    data = base64.b64decode(case["in"])
+    ret, out = same(g, props, data)
+    # the real plugin's bytes directly, behind the reference processor's pass over a unit's buffer: the filter's output, or -- where
+    # it answered NOTOUCH -- its input
+    assert mm.processor_output(out if ret == g.MODIFIED else data) == base64.b64decode(case["out"])
 
 
-def rnd_val(r, depth=0):
-    c = r.randrange(12 if depth < 2 else 9)
-    if c == 0:
-        return r.choice([b"", b"sample", b"abc", b"500", b"200", b"true", "café".encode(), b"x" * r.randrange(40)])
-    if c == 1:
-        return synth.Raw(b"\xc4" + bytes([3]) + b"abc")
-    if c == 2:
-        return r.choice([0, 1, 127, 128, 255, 256, 65535, 65536, 2 ** 32, 2 ** 63])
-    if c == 3:
-        return r.choice([-1, -32, -33, -128, -129, -32768, -32769, -2 ** 31, -2 ** 31 - 1])
-    if c == 4:
-        return synth.Raw(b"\xd0\x05")                 # a non-negative value in the signed family
-    if c == 5:
-        return synth.Raw(b"\xca" + struct.pack(">f", 1.5))
-    if c == 6:
-        return r.random() * 1000
-    if c == 7:
-        return r.choice([True, False])
-    if c == 8:
-        return None
-    if c == 9:
-        return [rnd_val(r, depth + 1) for _ in range(r.randrange(4))]
-    if c == 10:
-        return {r.choice(KEYS): rnd_val(r, depth + 1) for _ in range(r.randrange(4))}
-    return synth.KV([(r.choice(KEYS), rnd_val(r, depth + 1)) for _ in range(r.randrange(4))])
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 127, 128, 129, 1025])
+def test_wave_edges(g, n):
+    data = mc.wave_rows(n)
+    for props in (mc.W_COND, mc.W_PLAIN):
+        m = mm.Model(props)
+        m.filter(data)
+        assert same(g, props, data)[0] == g.MODIFIED
+        # rows 0, 3, .. are rebuilt; 1, 4, .. have no "go" (the condition is false / Remove finds nothing, the other rules apply);
+        # 2, 5, .. carry a time the encoder refuses
+        rebuilt = sum(1 for i in range(n) if i % 3 == 0) if props is mc.W_COND else sum(1 for i in range(n) if i % 3 != 2)
+        assert m.stats.get("rebuilt", 0) == rebuilt and m.counts() == (n, n)
 
 
-def rnd_record(r):
-    body = synth.KV([(r.choice(KEYS) if r.random() < 0.9 else r.choice([True, 7]), rnd_val(r)) for _ in range(r.randrange(8))])
-    kind = r.randrange(8)
-    if kind == 0:
-        return synth.mp([r.randrange(2 ** 33), body])                          # legacy, integer time
-    if kind == 1:
-        return synth.mp([1700000000.25, body])                                 # legacy, float time
-    if kind == 2:
-        return synth.mp([[synth.ext_ts(5, 6), {"m": 1, "z": [1, 2]}], body])    # metadata
-    if kind == 3 and r.random() < 0.3:
-        return synth.mp([[synth.Raw(b"\xd7\x00\xff\xff\xff\xff\x00\x00\x00\x00"), {}], {}])   # group marker
-    return synth.mp([[synth.ext_ts(r.randrange(2 ** 32), r.randrange(10 ** 9)), {}], body])
+# programs with g rules that can add an entry (Add, Set, Copy, Hard_copy): a body of 32 - g entries fills the last LDS slot.  In the
+# first of each group every such rule applies (final lists of 31, 32 and 33 entries); in the others some do not (Add of a present
+# key, Copy of an absent source) and the room is asked for all the same.  Move_to_start and Hard_copy shift entries across the list.
+LIST_PROGRAMS = [
+    (1, [("Add", "new1 v"), ("Move_to_start", "e1")]),
+    (1, [("Hard_copy", "src new4"), ("Move_to_start", "e1")]),
+    (1, [("Add", "src v"), ("Move_to_start", "e1"), ("Remove", "e4")]),
+    (1, [("Copy", "absent new3"), ("Move_to_end", "s")]),
+    (4, [("Add", "new1 v"), ("Set", "new2 v"), ("Copy", "src new3"), ("Hard_copy", "src new4"), ("Move_to_start", "e1")]),
+    (4, [("Add", "src v"), ("Copy", "absent new3"), ("Hard_copy", "src e2"), ("Set", "e0 v"), ("Move_to_start", "e1")]),
+    (4, [("Hard_copy", "e5 e0"), ("Move_to_end", "s"), ("Add", "n v"), ("Set", "src w"), ("Copy", "e3 e3b")]),
+]
 
 
-def rnd_word(r):
-    return r.choice([k.decode() or "''" for k in KEYS] + ["^a", "b$", "^k[0-9]$", "/^A/i", "x|y"])
+@pytest.mark.parametrize("grow,props", LIST_PROGRAMS, ids=["%d-%d" % (p[0], i) for i, p in enumerate(LIST_PROGRAMS)])
+def test_lds_list_boundary(g, grow, props):
+    assert sum(1 for name, _ in props if name in ("Add", "Set", "Copy", "Hard_copy")) == grow
+    lim = 32 - grow
+    data = mc.list_rows(130, [lim - 1, lim, lim + 1])
+    assert same(g, props, data)[0] == g.MODIFIED
+    if props is LIST_PROGRAMS[0][1] or props is LIST_PROGRAMS[4][1]:
+        out = synth.unpack_all(same(g, props, data)[1])
+        assert sorted({len(body[1]) for _, body in out if len(body[1]) > 4}) == [31, 32, 33]
 
 
-def rnd_program(r):
-    props = []
-    for _ in range(r.randrange(5)):
-        t = r.choice(mm.CONDS)
-        if mm.a_rx(mm.CONDS.index(t)):
-            props.append(("Condition", "%s %s %s" % (t, r.choice(["^a", "^k", "^re", "true", "."]), r.choice(["^s", "0", "t", "."]))))
-        else:
-            props.append(("Condition", "%s %s %s" % (t, r.choice(["a", "$a", "k1", "$a['k'][0]", "$a['ab']", "$TAG", "log"]),
-                                                    r.choice(["sample", "^s", "abc", "''"]))))
-    for _ in range(r.randrange(1, 17)):
-        name = r.choice(list(mm.RULES1) + list(mm.RULES2))
-        if name in mm.RULES1:
-            w = rnd_word(r) if name == "remove_regex" else r.choice([k.decode() for k in KEYS if k] + ["r", "refe", "abx"])
-            props.append((name, w))
-        else:
-            a, b = r.choice([k.decode() for k in KEYS if k]), r.choice([k.decode() for k in KEYS if k])
-            if name == "hard_copy" and a == b:
-                b = b + "_2"
-            props.append((name, "%s %s" % (a, b)))
-    r.shuffle(props)
-    return props
+@pytest.mark.parametrize("n", [1024, 1025])
+def test_arena_exact_fit_and_regrow(g, n):
+    # rows of 64 entries and a program that adds none: a row asks the arena for exactly its 64 entries.  1024 rows ask for the 65 536
+    # entries a filter starts with and fit; 1025 rows make the arena grow
+    props = [("Move_to_end", "k1"), ("Rename", "k7 seven"), ("Remove_regex", "^k5")]
+    data = mc.rows_of_64(n)
+    want = mm.Model(props).filter(data)
+    assert want[0] == g.MODIFIED
+    f = g.FilterModify(props)
+    for _ in range(2):                                 # the second call sees the arena as the first one left it (trimmed if grown)
+        assert f.filter(data) == want
+        assert f.counts() == (n, n) and f.overread() == 0
+    # growth and a decoder error in one call: NOTOUCH, and the counts are those of the rows in front of the error
+    assert f.filter(mc.rows_of_64(1100, bad_at=700)) == (g.NOTOUCH, None)
+    assert f.counts() == (700, 700)
+    assert f.filter(data) == want
+    f.close()
 
 
-def test_fuzz(g):
-    r = random.Random(1234)
-    modified = 0
-    for it in range(150):
-        props = rnd_program(r)
-        data = b"".join(rnd_record(r) for _ in range(r.randrange(1, 60)))
-        got = same(g, props, data)
-        modified += got is not None and got[0] == g.MODIFIED
-    assert modified > 30
+OVER = synth.mp([[synth.ext_ts(1, 2), {}], synth.KV([(b"x", b"y"), (b"ab", 1)])])          # "ab\x01z" runs past this record's end
+GOOD = synth.mp([[synth.ext_ts(1, 3), {}], synth.KV([(b"abc", 1), (b"ab\x01zz", 2), (b"k", b"v")])])
+
+
+@pytest.mark.parametrize("at", [0, 1, 63, 64, 65, 199])
+def test_decoder_error_positions(g, at):
+    props = [("Remove_wildcard", "ab\x01z"), ("Set", "k x")]
+    bad = synth.mp([[synth.ext_ts(1, 0), {}], "not a map"])
+    rows = [GOOD] * 200
+    rows[at] = bad
+    before, behind = (at - 1 if at else None), (at + 1 if at < 199 else None)
+    for i in (before, behind):
+        if i is not None:
+            rows[i] = OVER
+    data = b"".join(rows)
+    f = g.FilterModify(props)
+    assert f.filter(data) == (g.NOTOUCH, None)         # although every record in front of the error was rebuilt
+    assert f.counts() == (at, at)
+    assert f.overread() == (1 if before is not None else 0)
+    f.close()
+    assert same(g, props, data) == (g.NOTOUCH, None)
+    # without the bad row the same rows are MODIFIED and both overreads count
+    rows[at] = GOOD
+    assert same(g, props, b"".join(rows))[0] == g.MODIFIED
+
+
+def test_cut_last_record(g):
+    case = [c for c in REF_CASES if c["name"] == "garbage_cut_record"][0]
+    data = base64.b64decode(case["in"])
+    got = same(g, [tuple(p) for p in case["props"]], data)
+    # the golden holds the one whole record as it came in, although the rule applies to it: the plugin answered NOTOUCH
+    assert got == (g.NOTOUCH, None) and base64.b64decode(case["out"]) == mm.processor_output(data) != b""
+    # 70 whole records and one cut inside a payload: NOTOUCH; cut behind the payload's header, msgpack-c has consumed all it was
+    # given, the decoder's offset stands at the end and the call is MODIFIED (the golden's garbage_cut_behind_header)
+    whole, last = b"".join([GOOD] * 70), synth.mp([[synth.ext_ts(1, 4), {}], {"k": "long value"}])
+    f = g.FilterModify([("Set", "k x")])
+    assert f.filter(whole + last[:-4]) == (g.NOTOUCH, None) and f.counts() == (70, 70)
+    f.close()
+    assert same(g, [("Set", "k x")], whole + last[:-4]) == (g.NOTOUCH, None)
+    assert same(g, [("Set", "k x")], whole + last[:-10])[0] == g.MODIFIED
+
+
+@pytest.mark.parametrize("seed", mc.FUZZ_SEEDS)
+def test_fuzz(g, seed):
+    # (tests/test_modify_ref.py holds the generator to its floors on the model: rows rebuilt and raw, every rule, every condition)
+    r = random.Random(seed)
+    for _ in range(40):
+        props = mc.rnd_program(r)
+        f, m = g.FilterModify(props), mm.Model(props)
+        for _ in range(3):
+            data = b"".join(mc.rnd_record(r) for _ in range(r.randrange(1, 61)))
+            got, want = f.filter(data), m.filter(data)
+            assert got == want, (props, got[0], want[0])
+            assert f.counts() == m.counts()
+        assert f.overread() == m.stats.get("overread", 0) == 0
+        f.close()
+
+
+def test_rows_an_earlier_filter_dropped(g):
+    n = 200
+    drop = {0, 63, 64, n - 1}
+    blob = b"".join(synth.mp([[synth.ext_ts(1700000000 + i, i), {}], synth.KV([(b"lvl", b"drop" if i in drop else b"keep"), (b"n%d" % (i % 5), i),
+                                                                               (b"k", b"v")])]) for i in range(n))
+    grep = [("exclude", "lvl ^drop$")]
+    props = [("Condition", "Key_exists n1"), ("Set", "k x"), ("Move_to_start", "n"), ("Copy", "lvl level")]
+    fg, fm = g.FilterGrep(grep), g.FilterModify(props)
+    w1 = ob.Grep(grep).filter(blob)[1]
+    assert len(synth.unpack_all(w1)) == n - 4
+    chain = g.FilterChain([fg, fm])
+    r, out = chain.filter(blob)
+    m = mm.Model(props)
+    assert (r, out) == m.filter(w1) and r == g.MODIFIED
+    st = chain.last_stats()[1]
+    assert (st["in_records"], st["out_records"]) == m.counts() == (n - 4, n - 4)
+    assert fm.overread() == 0
+    fm.close()
 
 
 def test_prefix_quirk(g):
