@@ -76,6 +76,11 @@ def lib():
     L.flbgpu_nest_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
     L.flbgpu_nest_counters.restype = None
     L.flbgpu_nest_counters.argtypes = [c_void_p, POINTER(c_uint64)]
+    L.flbgpu_filter_type_converter_create.restype = c_void_p
+    L.flbgpu_filter_type_converter_create.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p)]
+    L.flbgpu_type_converter_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
+    L.flbgpu_type_converter_counters.restype = None
+    L.flbgpu_type_converter_counters.argtypes = [c_void_p, POINTER(c_uint64)]
     L.flbgpu_filter_destroy.argtypes = [c_void_p]
     L.flbgpu_filter_run.argtypes = [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]
     L.flbgpu_filter_run_dev.argtypes = [c_void_p, POINTER(DevChunk), POINTER(DevChunk), c_void_p]
@@ -382,6 +387,31 @@ def nest_parse_check(props):
     """the program configure() builds from props as one line of text (host only); raises ValueError where create refuses"""
     buf = ctypes.create_string_buffer(1 << 17)
     if lib().flbgpu_nest_parse_check(*_props(props), buf, len(buf)) != 0:
+        raise ValueError(last_error())
+    return buf.value.decode()
+
+
+class FilterTypeConverter(_Filter):
+    """filter_type_converter: props = [(name, value), ...] in configuration order, e.g. [("str_key", "status status_i int"),
+    ("int_key", "size size_s string")] (plugins/filter_type_converter/type_converter.c:57-140)"""
+
+    def __init__(self, props):
+        self.h = lib().flbgpu_filter_type_converter_create(*_props(props))
+        if not self.h:
+            raise ValueError("flbgpu_filter_type_converter_create: " + last_error())
+
+    def counters(self):
+        """(conversions done, conversions failed, conversions C leaves undefined, size/emit mismatches) since the filter was created
+        (flb_gpu.h flbgpu_type_converter_counters)"""
+        o = (c_uint64 * 4)()
+        lib().flbgpu_type_converter_counters(self.h, o)
+        return tuple(int(x) for x in o)
+
+
+def type_converter_parse_check(props):
+    """the rules configure() keeps from props, in its order, as one line of text (host only); raises ValueError where create refuses"""
+    buf = ctypes.create_string_buffer(1 << 17)
+    if lib().flbgpu_type_converter_parse_check(*_props(props), buf, len(buf)) != 0:
         raise ValueError(last_error())
     return buf.value.decode()
 

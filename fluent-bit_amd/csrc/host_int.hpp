@@ -90,6 +90,8 @@ int simulate_fx3(const std::vector<uint8_t> &b, const DevFx &fx, int ncap, const
 int simulate_fx4(const std::vector<uint8_t> &b, const DevFx &fx, int ncap, const uint8_t *s, uint32_t len, uint16_t *caps);
 // grammar: src/record_accessor/ra.l:54-67, ra.y:60-99
 bool parse_ra(const char *pat, DevKey &k, std::string &why);
+// flb_slist_split_tokens(list, str, max) (src/flb_slist.c:182-217; recmod.cpp): `max` tokens, then the rest of the line as one more entry
+void slist_split_tokens(const std::string &s, int max, std::vector<std::string> &out);
 // "<field> <regex>" rule of filter_grep / filter_log_to_metrics -> device rule (tables uploaded into blobs)
 bool compile_rule(const std::string &ra_field, const char *pattern, GrepRule &r, std::vector<TableBlob *> &blobs, std::string &why, bool *nonregular = nullptr);
 
@@ -139,7 +141,7 @@ uint64_t l2m_limbs_bits(const uint64_t *limbs, uint64_t n_nan, uint64_t n_pinf, 
 struct KernelProf { const char *name; double ms = 0; uint64_t launches = 0; };
 struct ProfPending { const char *name; hipEvent_t e0, e1; };
 
-enum { F_PARSER = 1, F_GREP = 2, F_L2M = 3, F_JSONFMT = 4, F_MODIFY = 5, F_RECMOD = 6, F_NEST = 7 };
+enum { F_PARSER = 1, F_GREP = 2, F_L2M = 3, F_JSONFMT = 4, F_MODIFY = 5, F_RECMOD = 6, F_NEST = 7, F_TYPECONV = 8 };
 
 struct ModState;                 // filter_modify's program and buffers (modify.cpp)
 void mod_state_destroy(ModState *);
@@ -147,6 +149,8 @@ struct RecmodState;              // filter_record_modifier's program and buffers
 void recmod_state_destroy(RecmodState *);
 struct NestState;                // filter_nest's program and buffers (nest.cpp)
 void nest_state_destroy(NestState *);
+struct TypeconvState;            // filter_type_converter's program and buffers (typeconv.cpp)
+void typeconv_state_destroy(TypeconvState *);
 
 struct flbgpu_filter {
     int kind = 0;
@@ -216,6 +220,8 @@ struct flbgpu_filter {
     RecmodState *recmod = nullptr;
     // filter_nest
     NestState *nest = nullptr;
+    // filter_type_converter
+    TypeconvState *typeconv = nullptr;
     bool host_list = false;                     // filter_parser: a list of several parsers with host parsers in it (flbgpu.cpp host_list_rx)
     flbgpu::DevBuf d_hres[flbgpu::MAX_HOST_PARSERS];   // their answers for the chunk at hand
     // msgpack -> JSON output formatter (packfmt.cpp)
@@ -239,6 +245,7 @@ struct flbgpu_filter {
         mod_state_destroy(mod);
         recmod_state_destroy(recmod);
         nest_state_destroy(nest);
+        typeconv_state_destroy(typeconv);
         for (auto *b : rule_blobs) delete b;
         for (auto *b : host_rx) if (b) rx::bt_free(b);
         delete l2m_gate;
@@ -290,6 +297,9 @@ bool run_modify_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chu
 bool run_recmod_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
 // filter_nest entry (nest.cpp)
 bool run_nest_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
+
+// filter_type_converter entry (typeconv.cpp)
+bool run_typeconv_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
 
 // filter_log_to_metrics entry used by flbgpu_filter_run / flbgpu_filter_run_dev
 bool run_l2m_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, hipStream_t st, int *ret);

@@ -220,6 +220,9 @@ NC_HD void bits_to_me(uint64_t bits, bool mid, uint64_t &M, int64_t &E) {
 // scanner
 // ------------------------------------------------------------------------------------------
 enum { MODE_STRTOD = 0, MODE_SSCANF = 1 };
+// flag on top of a mode: nan(n-char-sequence) puts the sequence into the payload as glibc's strtod does (nan_payload below);
+// without it every NaN is the plain quiet NaN
+constexpr int MODE_NAN_PAYLOAD = 0x100;
 enum { NC_FAIL = 0, NC_OK = 1, NC_NEED_EXACT = 2 };
 
 NC_HD bool is_space(uint32_t c) { return c == ' ' || (c >= 9 && c <= 13); }
@@ -309,11 +312,37 @@ struct ScanResult {
     uint32_t consumed;   // bytes of the longest valid prefix (strtod's endptr); 0 = no conversion
 };
 
+// the payload glibc's strtod gives nan(n-char-sequence) (stdlib/strtod_nan_main.c): the sequence s[b .. e) -- letters, digits and
+// '_' -- read by strtoull with base 0; when that takes all of it, its low 51 bits go under the quiet bit (0: the plain NaN)
+template <class Src>
+NC_HD uint64_t nan_payload(const Src &s, uint32_t b, uint32_t e) {
+    uint32_t base = 10, i = b;
+    if (i < e && s[i] == '0') {
+        if (i + 1 < e && lower(s[i + 1]) == 'x') { base = 16; i += 2; }
+        else base = 8;
+    }
+    const uint64_t cutoff = ~0ull / base, cutlim = ~0ull % base;
+    uint64_t v = 0;
+    bool any = false, over = false;
+    for (; i < e; i++) {
+        const int d = hexval(s[i]);
+        if (d < 0 || (uint32_t) d >= base) break;
+        any = true;
+        if (v > cutoff || (v == cutoff && (uint64_t) d > cutlim)) over = true;
+        else v = v * base + (uint64_t) d;
+    }
+    if (!any || i != e) return 0;
+    if (over) v = ~0ull;
+    return v & ((1ull << 51) - 1);
+}
+
 // strtod() / sscanf("%lf") over s[0 .. len).  Reading stops at len or at a NUL byte.
 template <bool EXACT, class Src>
 NC_HD ScanResult scan_double(const Src &s, uint32_t len, int mode) {
     ScanResult r;
     r.status = NC_FAIL; r.bits = 0; r.consumed = 0;
+    const bool nan_payload_mode = (mode & MODE_NAN_PAYLOAD) != 0;
+    mode &= 0xff;
     uint32_t i = 0;
     // effective length: C strings end at the first NUL
     {
@@ -340,6 +369,7 @@ NC_HD ScanResult scan_double(const Src &s, uint32_t len, int mode) {
     if (c0 == 'n') {
         if (i + 3 <= len && lower(s[i + 1]) == 'a' && lower(s[i + 2]) == 'n') {
             uint32_t j = i + 3;
+            uint64_t payload = 0;
             if (j < len && s[j] == '(') {      // nan(n-char-sequence): accepted only when closed
                 uint32_t k = j + 1;
                 while (k < len) {
@@ -348,9 +378,12 @@ NC_HD ScanResult scan_double(const Src &s, uint32_t len, int mode) {
                     if (!alnum) break;
                     k++;
                 }
-                if (k < len && s[k] == ')') j = k + 1;
+                if (k < len && s[k] == ')') {
+                    if (nan_payload_mode) payload = nan_payload(s, j + 1, k);
+                    j = k + 1;
+                }
             }
-            r.status = NC_OK; r.bits = sign | DBL_NAN_BITS; r.consumed = j;
+            r.status = NC_OK; r.bits = sign | DBL_NAN_BITS | payload; r.consumed = j;
         }
         return r;
     }
@@ -708,6 +741,96 @@ NC_HD_NOINL int fmt_json_double(uint64_t bits, bool nan_to_null, Dst &out) {
         return 4;
     }
     return fmt_g16(bits, out);
+}
+
+
+// ------------------------------------------------------------------------------------------
+// strtoimax / strtoumax (glibc stdlib/strtol_l.c), base 10 or 16, over s[0 .. len): reading stops at len or at a NUL byte.
+// Leading isspace bytes, one optional sign, with base 16 an optional 0x / 0X; no digit at all is 0; trailing bytes are ignored.
+// Overflow saturates: INTMAX_MAX / INTMAX_MIN for the signed scan, UINTMAX_MAX (whatever the sign) for the unsigned one, which
+// otherwise negates a value behind '-' modulo 2^64.  The answer is the 64 bits of the result.
+// ------------------------------------------------------------------------------------------
+template <class Src>
+NC_HD uint64_t scan_intmax(const Src &s, uint32_t len, uint32_t base, bool is_signed) {
+    uint32_t i = 0;
+    while (i < len && is_space(s[i])) i++;
+    bool neg = false;
+    if (i < len && (s[i] == '-' || s[i] == '+')) { neg = s[i] == '-'; i++; }
+    if (base == 16 && i + 1 < len && s[i] == '0' && lower(s[i + 1]) == 'x') i += 2;
+    const uint64_t cutoff = ~0ull / base, cutlim = ~0ull % base;
+    uint64_t v = 0;
+    bool any = false, over = false;
+    for (; i < len; i++) {
+        const uint32_t c = s[i];
+        const int d = base == 16 ? hexval(c) : (c >= '0' && c <= '9' ? (int) c - '0' : -1);
+        if (d < 0) break;
+        any = true;
+        if (v > cutoff || (v == cutoff && (uint64_t) d > cutlim)) over = true;
+        else v = v * base + (uint64_t) d;
+    }
+    if (!any) return 0;
+    if (is_signed) {
+        const uint64_t lim = neg ? (1ull << 63) : (1ull << 63) - 1;
+        if (over || v > lim) return lim;
+    }
+    else if (over) return ~0ull;
+    return neg ? 0 - v : v;
+}
+
+// "%lu": writes at most 20 characters, returns the count
+template <class Dst>
+NC_HD int fmt_lu(uint64_t u, Dst &out) {
+    char tmp[20];
+    int n = 0, w = 0;
+    do { tmp[n++] = (char) ('0' + u % 10); u /= 10; } while (u);
+    while (n > 0) { out.put((uint32_t) (uint8_t) tmp[--n]); w++; }
+    return w;
+}
+
+// (double) of a 64-bit integer: round to nearest even, as the C cast does
+NC_HD uint64_t u64_to_double_bits(uint64_t v) { return v ? make_double_bits(v, 0, false) : 0; }
+NC_HD uint64_t i64_to_double_bits(int64_t v) {
+    return v < 0 ? DBL_SIGN | make_double_bits((uint64_t) 0 - (uint64_t) v, 0, false) : u64_to_double_bits((uint64_t) v);
+}
+
+// the magnitude of a finite binary64, truncated towards zero; false when it is 2^64 or more
+NC_HD bool trunc_mag(uint64_t mag, uint64_t &t) {
+    uint64_t M;
+    int64_t E;
+    bits_to_me(mag, false, M, E);
+    if (E >= 0) {
+        if (E > 11) return false;
+        t = M << E;
+        return true;
+    }
+    t = -E >= 64 ? 0 : M >> -E;
+    return true;
+}
+
+// (int64_t) of a binary64 as x86-64 performs it (cvttsd2si): a NaN and a value the target cannot hold give INT64_MIN.  undef: C
+// leaves the conversion undefined -- NaN or |v| >= 2^63 (-2^63 itself is counted with them; its answer is the right one)
+NC_HD uint64_t double_to_i64_x86(uint64_t bits, bool &undef) {
+    const uint64_t mag = bits & ~DBL_SIGN;
+    uint64_t t = 0;
+    if (mag >= DBL_INF_BITS || !trunc_mag(mag, t) || t >= (1ull << 63)) { undef = true; return 1ull << 63; }
+    return (bits & DBL_SIGN) ? 0 - t : t;
+}
+
+// (uint64_t) of a binary64 as gcc compiles it for x86-64 without AVX-512: below 2^63 (a NaN compares so) cvttsd2si of the value,
+// from 2^63 on cvttsd2si of (value - 2^63) with the top bit flipped.  undef: NaN, v <= -1 or v >= 2^64
+NC_HD uint64_t double_to_u64_x86(uint64_t bits, bool &undef) {
+    const uint64_t mag = bits & ~DBL_SIGN;
+    const bool neg = (bits & DBL_SIGN) != 0;
+    uint64_t t = 0;
+    if (mag > DBL_INF_BITS) { undef = true; return 1ull << 63; }
+    const bool fits = mag < DBL_INF_BITS && trunc_mag(mag, t);
+    if (neg) {
+        if (!fits || t >= (1ull << 63)) { undef = true; return 1ull << 63; }
+        if (t >= 1) undef = true;
+        return 0 - t;
+    }
+    if (!fits) { undef = true; return 0; }          // value - 2^63 >= 2^63: INT64_MIN, its top bit flipped
+    return t;
 }
 
 }  // namespace nc

@@ -33,6 +33,30 @@ int flbgpu_nc_fmt_json_double(double v, int nan_to_null, char *buf) {
     BufDst d{buf, 0};
     return fmt_json_double(bits, nan_to_null != 0, d);
 }
+// strtoimax (is_signed) / strtoumax over s[0 .. len), base 10 or 16: the 64 bits of the answer
+unsigned long long flbgpu_nc_scan_intmax(const char *s, int len, int base, int is_signed) {
+    PtrSrc src{(const uint8_t *) s};
+    return scan_intmax(src, (uint32_t) len, (uint32_t) base, is_signed != 0);
+}
+int flbgpu_nc_fmt_lu(unsigned long long v, char *buf) {
+    BufDst d{buf, 0};
+    return fmt_lu((uint64_t) v, d);
+}
+// (double) of an integer, (int64_t) / (uint64_t) of a double as x86-64 answers; *undef is set where C leaves it undefined
+double flbgpu_nc_int_to_double(unsigned long long v, int is_signed) {
+    const uint64_t bits = is_signed ? i64_to_double_bits((int64_t) v) : u64_to_double_bits((uint64_t) v);
+    double d;
+    memcpy(&d, &bits, 8);
+    return d;
+}
+unsigned long long flbgpu_nc_double_to_int(double v, int is_signed, int *undef) {
+    uint64_t bits;
+    memcpy(&bits, &v, 8);
+    bool u = false;
+    const uint64_t r = is_signed ? double_to_i64_x86(bits, u) : double_to_u64_x86(bits, u);
+    if (undef) *undef = u ? 1 : 0;
+    return r;
+}
 int flbgpu_nc_fmt_ld(long long v, char *buf) {
     BufDst d{buf, 0};
     return fmt_ld((int64_t) v, d);

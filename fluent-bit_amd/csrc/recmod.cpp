@@ -6,10 +6,8 @@
 
 using namespace flbgpu;
 
-namespace {
-
 // token_retrieve (src/flb_slist.c:107-180): one token of a line; *pos < 0 when the line has ended.  false: no token.
-bool next_token(const std::string &s, long *pos, std::string &tok) {
+static bool next_token(const std::string &s, long *pos, std::string &tok) {
     if (*pos < 0) return false;
     const char *b = s.c_str();
     const char *p = b + *pos;
@@ -48,8 +46,8 @@ bool next_token(const std::string &s, long *pos, std::string &tok) {
     return false;
 }
 
-// flb_slist_split_tokens(list, str, 2) (src/flb_slist.c:182-217): two tokens, then the rest of the line as a third entry
-void split_tokens2(const std::string &s, std::vector<std::string> &out) {
+// flb_slist_split_tokens(list, str, max) (src/flb_slist.c:182-217): `max` tokens, then the rest of the line as one more entry
+void flbgpu::slist_split_tokens(const std::string &s, int max, std::vector<std::string> &out) {
     out.clear();
     long pos = 0;
     int count = 0;
@@ -57,7 +55,7 @@ void split_tokens2(const std::string &s, std::vector<std::string> &out) {
     while (next_token(s, &pos, tok)) {
         out.push_back(tok);
         if (pos < 0) break;
-        if (++count >= 2) {
+        if (++count >= max) {
             const char *p = s.c_str() + pos;
             while (*p == ' ') p++;
             if (*p) out.emplace_back(p);
@@ -65,6 +63,8 @@ void split_tokens2(const std::string &s, std::vector<std::string> &out) {
         }
     }
 }
+
+namespace {
 
 struct RKey { std::string key; bool prefix; };
 struct RProgram {
@@ -87,7 +87,7 @@ bool parse_program(int nprops, const char *const *names, const char *const *valu
         const std::string name = names[i] ? names[i] : "", val = values[i] ? values[i] : "";
         if (!strcasecmp(name.c_str(), "record")) {
             std::vector<std::string> tok;
-            split_tokens2(val, tok);
+            slist_split_tokens(val, 2, tok);
             // SLIST_2: fewer than two entries fail the config map's size check (src/flb_config_map.c:32-59) and the filter does not
             // start; more than two pass it and configure() skips the entry with a message (:96-101)
             if (tok.size() < 2) { why = "Record needs 'KEY VALUE': " + val; return false; }

@@ -1,0 +1,346 @@
+// typeconv_kernels.inc -- filter_type_converter (plugins/filter_type_converter/type_converter.c:182-353, src/flb_typecast.c): a lane
+// per record.  ONE function, tc_record, writes a record into whatever sink it is given: the size pass hands it a CountSink, the emit
+// pass a TcSink that never stores outside the row's own [out_off[r], out_off[r + 1]).  Both passes therefore walk the same code; a
+// row whose emitted length is not its sized length (or that ran into the end of its room) is counted, not written past.  The
+// original entries go out as rm_walk / mp_canon re-pack them (runs of already-canonical entries as one span); behind them, for every
+// rule whose key the ORIGINAL body holds, to_key and the converted value -- or the value as it was when the conversion fails.
+// Nested values are never interpreted, only walked; the numbers come from numconv.hpp and write straight into the sink.
+// Included inside namespace flbgpu after kdev.inc and canon_walk.inc (rm_walk, RM_MAP_HDR).
+
+struct TcTable {
+    const LDS_AS uint32_t *w;       // the table's words in LDS
+    int nrules;
+};
+
+// the emit pass's sink: [p, limit) is the row's room.  Nothing is stored at or past limit; p keeps counting, so the caller sees
+// both facts -- how long the record would have been and whether a store was withheld.
+struct TcSink {
+    uint8_t *p, *limit;
+    bool over = false;
+    DEV TcSink(uint8_t *dst, uint8_t *lim) : p(dst), limit(lim) {}
+    DEV void note_exact() {}
+    DEV void put(uint32_t b) {
+        if (p < limit) *p = (uint8_t) b; else over = true;
+        p++;
+    }
+    DEV void put32(uint32_t v) { for (int i = 0; i < 4; i++) put((v >> (8 * i)) & 0xffu); }
+    DEV void copy(const uint8_t *src, uint32_t len) {
+        const uint64_t room = p < limit ? (uint64_t) (limit - p) : 0;
+        const uint32_t n = room < len ? (uint32_t) room : len;
+        ByteSink bs(p);
+        bs.copy(src, n);
+        if (n < len) over = true;
+        p += len;
+    }
+};
+
+// a span of the record of any length
+DEV void tc_span(CountSink &s, const uint8_t *, uint64_t len) { s.n += len; }
+DEV void tc_span(TcSink &s, const uint8_t *src, uint64_t len) {
+    while (len > 0x40000000ull) { s.copy(src, 0x40000000u); src += 0x40000000ull; len -= 0x40000000ull; }
+    s.copy(src, (uint32_t) len);
+}
+// the body's map32 header: its room is left open when the record begins and filled when the number of entries is known
+DEV uint8_t *tc_open_hdr(CountSink &s) { s.n += RM_MAP_HDR; return nullptr; }
+DEV uint8_t *tc_open_hdr(TcSink &s) { uint8_t *at = s.p; s.p += RM_MAP_HDR; return at; }
+DEV void tc_close_hdr(CountSink &, uint8_t *, uint64_t) {}
+DEV void tc_close_hdr(TcSink &s, uint8_t *at, uint64_t n) {
+    TcSink hs(at, s.limit);
+    hs.put(0xdf);
+    pk_be(hs, n, 4);
+    if (hs.over) s.over = true;
+}
+
+template <class S> DEV void tc_put_lds(S &s, const LDS_AS uint32_t *e, uint32_t L) {
+    for (uint32_t j = 0; j < L; j++) s.put((e[j >> 2] >> (8 * (j & 3))) & 0xffu);
+}
+
+// are the L bytes at key (all of them inside the record: mp_tok checked the payload) the entry at e?  A 4-byte load is issued
+// only where 4 bytes remain inside the key.
+DEV bool tc_eq(const LDS_AS uint32_t *e, uint32_t L, const uint8_t *key) {
+    uint32_t j = 0;
+    bool eq = true;
+    for (; eq && j + 4 <= L; j += 4) eq = ldu32(key + j) == e[j >> 2];
+    for (; eq && j < L; j++) eq = ld8(key + j) == ((e[j >> 2] >> (8 * (j & 3))) & 0xffu);
+    return eq;
+}
+
+// ra_key_val_id (src/flb_ra_key.c:108-135): the value of the LAST entry of the map at `map` whose key is a STR equal to the name
+DEV const uint8_t *tc_find_last(const uint8_t *map, const uint8_t *end, const LDS_AS uint32_t *name, uint32_t nlen) {
+    Tok m = mp_tok(map, end);
+    if (m.type != T_MAP) return nullptr;
+    const uint8_t *p = m.next, *found = nullptr;
+    for (uint32_t i = 0; i < m.len; i++) {
+        Tok k = mp_tok(p, end);
+        const uint8_t *v = mp_end_of(k, p, end, 2);
+        if (!v) return nullptr;
+        if (k.type == T_STR && k.len == nlen && tc_eq(name, nlen, k.next)) found = v;
+        p = mp_end_of(mp_tok(v, end), v, end, 2);
+        if (!p) return nullptr;
+    }
+    return found;
+}
+
+// flb_ra_get_kv_pair (src/flb_record_accessor.c:788-801, src/flb_ra_key.c:151-236, 374-434) on the original body: the top-level
+// entry, then the sub-keys when its value is a map or an array (any other value is taken as it is).  A path that ends on an array
+// index has no key object, and the filter reads that as "not found" (type_converter.c:277-281).
+DEV const uint8_t *tc_lookup(const TcTable &tb, int ri, const uint8_t *body, const uint8_t *end) {
+    const LDS_AS uint32_t *r = tb.w + TC_RULE_WORDS * (uint32_t) ri;
+    if (r[0] & TC_INERT) return nullptr;
+    const uint8_t *val = tc_find_last(body, end, tb.w + (r[2] >> 2), r[1]);
+    if (!val) return nullptr;
+    const uint32_t nsub = (r[0] >> 16) & 0xffu;
+    Tok t = mp_tok(val, end);
+    if ((t.type != T_MAP && t.type != T_ARRAY) || nsub == 0) return val;
+    const LDS_AS uint32_t *sub = tb.w + (r[5] >> 2);
+    const uint8_t *cur = val;
+    uint32_t matched = 0;
+    bool last_index = false;
+    for (uint32_t s = 0; s < nsub; s++) {
+        Tok c = mp_tok(cur, end);
+        const uint32_t s0 = sub[2 * s];
+        if (s0 & TC_SUB_INDEX) {
+            const uint32_t idx = s0 & ~TC_SUB_INDEX;
+            if (c.type != T_ARRAY || idx >= c.len) return nullptr;
+            const uint8_t *p = c.next;
+            for (uint32_t i = 0; i < idx; i++) { p = mp_skip(p, end); if (!p) return nullptr; }
+            cur = p;
+            last_index = true;
+            if (++matched == nsub) break;
+            continue;
+        }
+        if (c.type != T_MAP) break;
+        const uint8_t *v = tc_find_last(cur, end, tb.w + (sub[2 * s + 1] >> 2), s0);
+        if (!v) continue;                          // "try next entry": the levels are never completed
+        cur = v;
+        last_index = false;
+        if (++matched == nsub) break;
+    }
+    if (matched != nsub || last_index) return nullptr;
+    return cur;
+}
+
+struct TcSrc {
+    const uint8_t *p;
+    uint32_t n;
+    DEV uint32_t operator[](uint32_t i) const { return i < n ? ld8(p + i) : 0u; }
+};
+struct TcDigits { uint32_t n = 0; DEV void put(uint32_t) { n++; } };
+template <class S> struct TcDst { S &s; DEV void put(uint32_t c) { s.put(c); } };
+
+template <class S> DEV void tc_f64(S &s, uint64_t bits) { s.put(0xcb); pk_be(s, bits, 8); }
+
+// flb_typecast_pack (src/flb_typecast.c:396-457, 72-341) of the value at v under rule word r0: true when the converted value was
+// written, false when nothing was (the caller writes the value as it is)
+template <class S> DEV bool tc_convert(uint32_t r0, const uint8_t *v, const uint8_t *end, S &s, bool &undef) {
+    const uint32_t src = r0 & 0xffu, to = (r0 >> 8) & 0xffu;
+    Tok t = mp_tok(v, end);
+    if (src == TC_SRC_STR) {
+        if (t.type != T_STR) return false;
+        TcSrc in{t.next, t.len};
+        switch (to) {
+        case TC_TO_INT: {
+            const uint64_t x = nc::scan_intmax(in, t.len, 10, true);
+            if (x == 0) return false;
+            pk_int(s, (int64_t) x);
+            return true;
+        }
+        case TC_TO_UINT: case TC_TO_HEX: {
+            const uint64_t x = nc::scan_intmax(in, t.len, to == TC_TO_HEX ? 16u : 10u, false);
+            if (x == 0) return false;
+            pk_uint(s, x);
+            return true;
+        }
+        case TC_TO_FLOAT: {
+            const nc::ScanResult sr = nc::scan_double<true>(in, t.len, nc::MODE_STRTOD | nc::MODE_NAN_PAYLOAD);
+            tc_f64(s, sr.status == nc::NC_OK ? sr.bits : 0);          // atof: no conversion is 0.0
+            return true;
+        }
+        case TC_TO_BOOL: {
+            const uint32_t c0 = nc::lower(in[0]), c1 = nc::lower(in[1]), c2 = nc::lower(in[2]), c3 = nc::lower(in[3]), c4 = nc::lower(in[4]);
+            if (t.len >= 4 && c0 == 't' && c1 == 'r' && c2 == 'u' && c3 == 'e') { s.put(0xc3); return true; }
+            if (t.len >= 5 && c0 == 'f' && c1 == 'a' && c2 == 'l' && c3 == 's' && c4 == 'e') { s.put(0xc2); return true; }
+            return false;
+        }
+        default: return false;
+        }
+    }
+    if (src == TC_SRC_INT || src == TC_SRC_UINT) {
+        if (t.type != T_UINT && t.type != T_NINT) return false;
+        const bool sgn = src == TC_SRC_INT;
+        switch (to) {
+        case TC_TO_STR: {
+            TcDigits d;
+            if (sgn) nc::fmt_ld((int64_t) t.u, d); else nc::fmt_lu(t.u, d);
+            pk_str_hdr(s, d.n);
+            TcDst<S> o{s};
+            if (sgn) nc::fmt_ld((int64_t) t.u, o); else nc::fmt_lu(t.u, o);
+            return true;
+        }
+        case TC_TO_FLOAT: tc_f64(s, sgn ? nc::i64_to_double_bits((int64_t) t.u) : nc::u64_to_double_bits(t.u)); return true;
+        case TC_TO_UINT: if (!sgn) return false; pk_uint(s, t.u); return true;
+        case TC_TO_INT: if (sgn) return false; pk_int(s, (int64_t) t.u); return true;
+        default: return false;
+        }
+    }
+    if (t.type != T_F32 && t.type != T_F64) return false;
+    const uint64_t bits = t.type == T_F64 ? t.u : (uint64_t) __double_as_longlong((double) __uint_as_float((uint32_t) t.u));
+    switch (to) {
+    case TC_TO_STR: {
+        TcDigits d;
+        nc::fmt_json_double(bits, false, d);
+        pk_str_hdr(s, d.n);
+        TcDst<S> o{s};
+        nc::fmt_json_double(bits, false, o);
+        return true;
+    }
+    case TC_TO_INT: pk_int(s, (int64_t) nc::double_to_i64_x86(bits, undef)); return true;
+    case TC_TO_UINT: pk_uint(s, nc::double_to_u64_x86(bits, undef)); return true;
+    default: return false;
+    }
+}
+
+struct TcRow {
+    bool bad, decoded;
+    uint32_t done, failed, undef;
+    uint64_t len;                       // output bytes (0: nothing emitted)
+};
+
+// the time the encoder writes: flb_log_event_encoder_set_timestamp refuses a time outside the EventTime range, its answer is
+// overwritten (:252-257) and the record goes out with the zero time begin_record left
+DEV void tc_time(const Event &ev, uint32_t &sec, uint32_t &nsec) {
+    const bool ok = ev.sec >= 0 && (uint64_t) ev.sec <= 0xffffffffull && ev.nsec >= 0 && ev.nsec < 1000000000LL;
+    sec = ok ? (uint32_t) ev.sec : 0;
+    nsec = ok ? (uint32_t) ev.nsec : 0;
+}
+
+// one record of the loop (:240-318) into s; false: the row is not one well-formed event
+template <class S> DEV bool tc_record(const TcTable &tb, const Event &ev, const uint8_t *end, S &s, TcRow &w) {
+    uint32_t sec, nsec;
+    tc_time(ev, sec, nsec);
+    s.put32(0x00d79292u);
+    s.put32(__builtin_bswap32(sec));
+    s.put32(__builtin_bswap32(nsec));
+    if (ev.meta) mp_canon(ev.meta, ev.meta_end, s); else s.put(0x80);
+    uint8_t *hdr = tc_open_hdr(s);
+    Tok bm = mp_tok(ev.body, end);
+    // the original entries, in order: runs of entries whose encoding is already canonical go out as one span
+    const uint8_t *p = bm.next, *span = nullptr;
+    for (uint32_t i = 0; i < bm.len; i++) {
+        const uint8_t *e0 = p;
+        uint64_t es = 0;
+        bool canon = true;
+        const uint8_t *v = rm_walk(p, end, 2, es, canon);
+        if (!v) return false;
+        p = rm_walk(v, end, 2, es, canon);
+        if (!p) return false;
+        if (canon) { if (!span) span = e0; continue; }
+        if (span) { tc_span(s, span, (uint64_t) (e0 - span)); span = nullptr; }
+        mp_canon(e0, end, s, 2);
+        mp_canon(v, end, s, 2);
+    }
+    if (p != end) return false;                                       // the row is one event and nothing else
+    if (span) tc_span(s, span, (uint64_t) (p - span));
+    uint64_t found = 0;
+    for (int ri = 0; ri < tb.nrules; ri++) {
+        const uint8_t *v = tc_lookup(tb, ri, ev.body, end);
+        if (!v) continue;
+        found++;
+        const LDS_AS uint32_t *r = tb.w + TC_RULE_WORDS * (uint32_t) ri;
+        tc_put_lds(s, tb.w + (r[4] >> 2), r[3]);
+        bool undef = false;
+        if (tc_convert(r[0], v, end, s, undef)) { w.done++; w.undef += undef ? 1u : 0u; }
+        else { w.failed++; mp_canon(v, end, s, 2); }
+    }
+    tc_close_hdr(s, hdr, (uint64_t) bm.len + found);
+    return true;
+}
+
+// size pass: rows an earlier filter dropped, group markers and decoder errors as rm_size treats them
+DEV TcRow tc_size(const TypeconvArgs &a, const TcTable &tb, uint64_t r) {
+    TcRow w;
+    w.bad = false; w.decoded = false; w.done = 0; w.failed = 0; w.undef = 0; w.len = 0;
+    const uint8_t *rec = a.data + a.row_off[r], *end = a.data + a.row_off[r + 1];
+    if (rec == end) return w;                                         // a record an earlier filter dropped
+    Event ev = decode_event(rec, end, true);
+    if (ev.flags & RF_BAD) { w.bad = true; return w; }
+    CountSink cs;
+    if (!tc_record(tb, ev, end, cs, w)) { w.bad = true; w.done = 0; w.failed = 0; w.undef = 0; return w; }
+    if (ev.flags & RF_SKIP) { w.done = 0; w.failed = 0; w.undef = 0; return w; }      // group markers: skipped by the decoder
+    w.decoded = true;
+    w.len = cs.n;
+    return w;
+}
+
+// emit pass: the record whose length the size pass wrote, into its own room and no further; true: the lengths agree
+DEV bool tc_emit(const TypeconvArgs &a, const TcTable &tb, uint64_t r) {
+    const uint8_t *rec = a.data + a.row_off[r], *end = a.data + a.row_off[r + 1];
+    Event ev = decode_event(rec, end, true);
+    if (ev.flags & RF_BAD) return false;
+    uint8_t *o0 = a.out + a.out_off[r], *o1 = a.out + a.out_off[r + 1];
+    TcSink bs(o0, o1);
+    TcRow w;
+    w.bad = false; w.decoded = false; w.done = 0; w.failed = 0; w.undef = 0; w.len = 0;
+    const bool ok = tc_record(tb, ev, end, bs, w);
+    return ok && !bs.over && bs.p == o1;
+}
+
+DEV unsigned long long tc_wave_sum(unsigned long long v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+template <bool EMIT>
+__global__ void __launch_bounds__(TC_BLOCK) k_typeconv(TypeconvArgs a) {
+    LDS_AS uint32_t *lds = (LDS_AS uint32_t *) g_lds;
+    for (uint32_t i = threadIdx.x; i < a.table_bytes / 4; i += TC_BLOCK) lds[i] = a.table[i];
+    __syncthreads();
+    TcTable tb{lds, a.nrules};
+    const uint64_t gsz = (uint64_t) gridDim.x * TC_BLOCK;
+    const uint32_t lane = threadIdx.x & 63u;
+    unsigned long long n_dec = 0, n_out = 0, n_done = 0, n_failed = 0, n_undef = 0, n_big = 0, n_mis = 0;
+    // every wave walks in step (the trip count is the wave's, not the lane's): the ballots below see whole waves
+    for (uint64_t r0 = (uint64_t) blockIdx.x * TC_BLOCK + (threadIdx.x & ~63u); r0 < a.n; r0 += gsz) {
+        const uint64_t r = r0 + lane;
+        const bool live = r < a.n;
+        if (EMIT) {
+            if (live && a.len[r] && !tc_emit(a, tb, r)) n_mis++;
+            continue;
+        }
+        TcRow w;
+        w.bad = false; w.decoded = false; w.done = 0; w.failed = 0; w.undef = 0; w.len = 0;
+        if (live) {
+            w = tc_size(a, tb, r);
+            const bool big = w.len > 0xFFFFFFFFull;                    // a row the u32 length column cannot hold
+            if (big) { n_big++; w.len = 0; }
+            a.len[r] = (uint32_t) w.len;
+            n_done += w.done; n_failed += w.failed; n_undef += w.undef;
+            if (w.bad) atomicMin(a.first_bad, (unsigned long long) r);
+        }
+        // the call-level facts of a wave's 64 records: counted by one lane from the ballots
+        const unsigned long long b_dec = __ballot(w.decoded), b_out = __ballot(w.len != 0);
+        if (lane == 0) { n_dec += __popcll(b_dec); n_out += __popcll(b_out); }
+    }
+    if (EMIT) {
+        if (n_mis) atomicAdd(&a.counts[6], n_mis);
+        return;
+    }
+    // one atomic per wave and counter that is not zero (every lane of the wave is here: the loop's trip count is the wave's)
+    n_done = tc_wave_sum(n_done); n_failed = tc_wave_sum(n_failed); n_undef = tc_wave_sum(n_undef);
+    if (lane == 0) {
+        if (n_dec) atomicAdd(&a.counts[0], n_dec);
+        if (n_out) atomicAdd(&a.counts[1], n_out);
+        if (n_done) atomicAdd(&a.counts[2], n_done);
+        if (n_failed) atomicAdd(&a.counts[3], n_failed);
+        if (n_undef) atomicAdd(&a.counts[4], n_undef);
+    }
+    if (n_big) atomicAdd(&a.counts[5], n_big);
+}
+
+void launch_typeconv(const TypeconvArgs &a, bool emit, hipStream_t st) {
+    if (a.n == 0) return;
+    uint64_t blocks = (a.n + TC_BLOCK - 1) / TC_BLOCK;
+    if (blocks > 65536) blocks = 65536;
+    if (emit) hipLaunchKernelGGL(k_typeconv<true>, dim3((unsigned) blocks), dim3(TC_BLOCK), a.table_bytes, st, a);
+    else hipLaunchKernelGGL(k_typeconv<false>, dim3((unsigned) blocks), dim3(TC_BLOCK), a.table_bytes, st, a);
+}

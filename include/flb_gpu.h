@@ -204,6 +204,48 @@ int flbgpu_nest_parse_check(int nprops, const char *const *names, const char *co
  * "no match" there), out[2] records the reference leaves undefined (sent as their own bytes), out[3] rows over 4 GB (nothing emitted) */
 void flbgpu_nest_counters(flbgpu_filter *f, uint64_t out[4]);
 
+/* ---- filter_type_converter: replaces cb_type_converter_init / cb_type_converter_filter / cb_type_converter_exit ----
+ * plugins/filter_type_converter/type_converter.c:57-106 (config_rule), 108-140 (configure, behind the config map of :366-388),
+ * 182-353 (one call); src/flb_typecast.c:27-49 (the type words), 72-341 (the conversions), 396-457 (the source-type checks);
+ * src/flb_record_accessor.c:74-230, 767-801 and src/flb_ra_key.c:108-236 (from_key).  (names[i], values[i]) are the instance's
+ * properties in configuration order, names without case, each may repeat:
+ *   str_key, int_key, uint_key, float_key   "from_key to_key type", split as flb_slist_split_tokens(.., 3) splits.  Fewer than three
+ *                  entries fail the config map and are refused.  A fourth entry (the rest of the line) makes config_rule answer -1,
+ *                  which configure() ignores (:121-132): the rule is skipped.  The rules run in configure()'s order -- every str_key, then every int_key,
+ *                  uint_key, float_key -- not in the configuration's.
+ *   type           a prefix, without case, of "int", "uint", "float", "hex", "string", "bool", tried in this order
+ *                  (strncasecmp over the word's own length, flb_typecast.c:27-49): "i", "u", "f", "h", "s", "str", "b" pass, the
+ *                  empty word is int, "integer" and "strings" are unknown.
+ *   from_key       a plain name, `$name`, `$name['a']['b']`, `$name['a'][1]`.  `pre$key` looks up `pre`, `$a.b` looks up `a`; `$TAG`,
+ *                  `$0`..`$9` and `$` make a rule that never finds its key.
+ * Refused, NULL + last_error: an unknown property, fewer than three entries, no rule left ("no rules", :134-137) -- and, although
+ * the reference accepts them, more than 64 rules, a rule table of more than 32768 bytes (it sits in LDS), a key name of 128 bytes or
+ * more, more than 8 sub-keys or 256 bytes of sub-key names, a `$name` that does not start with a letter or '_', and the two
+ * configurations at which the reference dies (config_rule unlinks a rule it never linked, :52, :95-100): a type word the type table
+ * does not know and a from_key the record accessor refuses.
+ * One call (:182-353): every decoded record is emitted again as 92 92 d7 00 <sec> <nsec> (a time outside the EventTime range goes out
+ * as 0.0: the encoder's refusal is overwritten, :252-257), the metadata as msgpack-c re-packs it, a map32 header
+ * (src/flb_mp.c:591-603), the original entries re-packed in their order, then for every rule whose key the ORIGINAL body holds (the
+ * LAST entry whose key is a STR equal to the name; sub-keys only through a map or array value; a path that ends on an array index
+ * finds nothing) to_key as STR and the converted value.  Conversions: str -> int / uint / hex (strtoimax / strtoumax; an answer of
+ * 0 is a failure, so "0" and "abc" fail), float (atof, never fails), bool ("true" / "false" as a prefix without case); int and uint
+ * (both take positive and negative integers, read as int64 / uint64) -> string, float, uint / int; float (float32 widened) ->
+ * string ("%.1f" for an integral value, else "%.16g"), int, uint.  Every other pair, and a value of another type, fails.  A failed
+ * conversion still appends to_key, followed by the value as it was.  float -> int / uint of a value the target cannot hold answers
+ * as x86-64 does (INT64_MIN; for uint gcc's sequence around 2^63) and is counted.  The call answers MODIFIED only when at least one
+ * conversion succeeded in the chunk AND the decoder's loop ended on a clean end of data (:321-346): a record the decoder refuses or
+ * undecodable bytes behind the records make it NOTOUCH.  Runs through flbgpu_filter_run[_dev], flbgpu_filter_chain_run[_dev],
+ * flbgpu_filter_last_counts (records decoded / records emitted) and flbgpu_filter_destroy. */
+flbgpu_filter *flbgpu_filter_type_converter_create(int nprops, const char *const *names, const char *const *values);
+/* host only, no device: the rules configure() keeps, in its order, as one line of text --
+ * "<str|int|uint|float>><int|uint|float|hex|string|bool>,K<hex name>{.<hex sub-key>|[<index>]}...|-,T<hex to_key>;..." ("-": the rule
+ * never finds a key) -- 0, or -1 + last_error where create refuses */
+int flbgpu_type_converter_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap);
+/* since the filter was created: out[0] conversions done, out[1] conversions failed (the value went out as it was), out[2]
+ * conversions C leaves undefined (float -> int / uint out of range), out[3] rows whose emitted length differed from their sized
+ * length (always 0; the emit pass never stores outside a row's room, and a call that counts one answers NOTOUCH) */
+void flbgpu_type_converter_counters(flbgpu_filter *f, uint64_t out[4]);
+
 /* ---- filter_log_to_metrics: replaces cb_log_to_metrics_init / cb_log_to_metrics_filter -----------
  * plugins/filter_log_to_metrics/log_to_metrics.c:655-968,970-1156.  (keys[i], values[i]) are the
  * instance's properties in configuration order; the ones read are regex / exclude (set_rules
