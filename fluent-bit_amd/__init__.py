@@ -81,6 +81,17 @@ def lib():
     L.flbgpu_type_converter_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
     L.flbgpu_type_converter_counters.restype = None
     L.flbgpu_type_converter_counters.argtypes = [c_void_p, POINTER(c_uint64)]
+    L.flbgpu_filter_rewrite_tag_create.restype = c_void_p
+    L.flbgpu_filter_rewrite_tag_create.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p)]
+    L.flbgpu_rewrite_tag_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
+    L.flbgpu_rewrite_tag_set_tag.restype = None
+    L.flbgpu_rewrite_tag_set_tag.argtypes = [c_void_p, c_char_p, c_int]
+    L.flbgpu_rewrite_tag_set_emitter.restype = None
+    L.flbgpu_rewrite_tag_set_emitter.argtypes = [c_void_p, c_void_p, c_void_p]
+    L.flbgpu_rewrite_tag_emitted.argtypes = [c_void_p, c_void_p]
+    L.flbgpu_rewrite_tag_emitted_dev.argtypes = [c_void_p, c_void_p]
+    L.flbgpu_rewrite_tag_counters.restype = None
+    L.flbgpu_rewrite_tag_counters.argtypes = [c_void_p, POINTER(c_uint64)]
     L.flbgpu_filter_destroy.argtypes = [c_void_p]
     L.flbgpu_filter_run.argtypes = [c_void_p, c_char_p, c_size_t, POINTER(c_void_p), POINTER(c_size_t)]
     L.flbgpu_filter_run_dev.argtypes = [c_void_p, POINTER(DevChunk), POINTER(DevChunk), c_void_p]
@@ -412,6 +423,80 @@ def type_converter_parse_check(props):
     """the rules configure() keeps from props, in its order, as one line of text (host only); raises ValueError where create refuses"""
     buf = ctypes.create_string_buffer(1 << 17)
     if lib().flbgpu_type_converter_parse_check(*_props(props), buf, len(buf)) != 0:
+        raise ValueError(last_error())
+    return buf.value.decode()
+
+
+class RtagEmittedRec(ctypes.Structure):
+    _fields_ = [("in_off", c_uint64), ("tag_off", c_uint64), ("len", ctypes.c_uint32), ("tag_len", ctypes.c_uint32)]
+
+
+class RtagEmitted(ctypes.Structure):
+    _fields_ = [("count", c_uint64), ("recs", c_void_p), ("tags", c_void_p), ("tag_bytes", c_uint64), ("input", c_void_p),
+                ("input_bytes", c_uint64)]
+
+
+RTAG_EMIT_CB = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t)
+
+
+class FilterRewriteTag(_Filter):
+    """filter_rewrite_tag: props = [(name, value), ...] in configuration order, e.g. [("Rule", "$log ^.*error.*$ err.$TAG false")]
+    (plugins/filter_rewrite_tag/rewrite_tag.c:112-190).  tag: the tag of the following calls; emitter: a function
+    (tag bytes, record bytes) -> int that stands where in_emitter_add_record stands -- an answer < 0 keeps the record"""
+
+    def __init__(self, props, tag=b"", emitter=None):
+        self.h = lib().flbgpu_filter_rewrite_tag_create(*_props(props))
+        if not self.h:
+            raise ValueError("flbgpu_filter_rewrite_tag_create: " + last_error())
+        self._cb = None
+        self.set_tag(tag)
+        if emitter is not None:
+            self.set_emitter(emitter)
+
+    def set_tag(self, tag):
+        tag = tag.encode() if isinstance(tag, str) else bytes(tag)
+        lib().flbgpu_rewrite_tag_set_tag(self.h, tag, len(tag))
+
+    def set_emitter(self, fn):
+        if fn is None:
+            self._cb = None
+            lib().flbgpu_rewrite_tag_set_emitter(self.h, None, None)
+            return
+        self._cb = RTAG_EMIT_CB(lambda ctx, tag, tag_len, buf, size: int(fn(ctypes.string_at(tag, tag_len), ctypes.string_at(buf, size))))
+        lib().flbgpu_rewrite_tag_set_emitter(self.h, ctypes.cast(self._cb, c_void_p), None)
+
+    def emitted(self):
+        """the last host-level call's accepted emissions: [(tag bytes, record bytes), ...] in record order"""
+        e = RtagEmitted()
+        if lib().flbgpu_rewrite_tag_emitted(self.h, byref(e)) != 0:
+            raise RuntimeError(last_error())
+        recs = ctypes.cast(e.recs, POINTER(RtagEmittedRec))
+        out = []
+        for i in range(e.count):
+            r = recs[i]
+            tag = ctypes.string_at(e.tags + r.tag_off, r.tag_len) if r.tag_len else b""
+            out.append((tag, ctypes.string_at(e.input + r.in_off, r.len) if e.input else (r.in_off, r.len)))
+        return out
+
+    def emitted_dev(self):
+        """after filter_dev: (count, device pointer of the table, device pointer of the tag arena, tag bytes)"""
+        e = RtagEmitted()
+        if lib().flbgpu_rewrite_tag_emitted_dev(self.h, byref(e)) != 0:
+            raise RuntimeError(last_error())
+        return int(e.count), e.recs, e.tags, int(e.tag_bytes)
+
+    def counters(self):
+        """(records emitted, emissions refused, size/emit mismatches, tag bytes written) since the filter was created
+        (flb_gpu.h flbgpu_rewrite_tag_counters)"""
+        o = (c_uint64 * 4)()
+        lib().flbgpu_rewrite_tag_counters(self.h, o)
+        return tuple(int(x) for x in o)
+
+
+def rewrite_tag_parse_check(props):
+    """the rules process_config builds from props as one line of text (host only); raises ValueError where create refuses"""
+    buf = ctypes.create_string_buffer(1 << 17)
+    if lib().flbgpu_rewrite_tag_parse_check(*_props(props), buf, len(buf)) != 0:
         raise ValueError(last_error())
     return buf.value.decode()
 

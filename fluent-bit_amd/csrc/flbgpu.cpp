@@ -2381,6 +2381,7 @@ static int run_any_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_
     else if (f->kind == F_RECMOD) ok = run_recmod_dev(f, in, out, st, &ret, garbage);
     else if (f->kind == F_NEST) ok = run_nest_dev(f, in, out, st, &ret, garbage);
     else if (f->kind == F_TYPECONV) ok = run_typeconv_dev(f, in, out, st, &ret, garbage);
+    else if (f->kind == F_RTAG) ok = run_rtag_dev(f, in, out, st, &ret, garbage);
     else ok = f->kind == F_PARSER ? run_parser_dev(f, in, out, st, &ret) : run_grep_dev(f, in, out, st, &ret, garbage);
     if (!ok) return FLBGPU_FILTER_NOTOUCH;      // errors degrade to NOTOUCH (SURVEY 8b "Errors")
     return ret;
@@ -2919,6 +2920,14 @@ extern "C" int flbgpu_filter_chain_run(flbgpu_filter *const *filters, int nfilte
     flbgpu_dev_chunk in, out;
     in.data = f->h_in_data.p; in.row_off = row_off; in.n = (uint64_t) n; in.bytes = consumed;
     memset(&out, 0, sizeof(out));
+    // filter_rewrite_tag instances ask their emitter on a host-level call, on the caller's bytes where their input is the caller's
+    struct RtagScope {
+        flbgpu_filter *const *fl; int n;
+        RtagScope(flbgpu_filter *const *fl_, int n_, const void *dev, const void *host) : fl(fl_), n(n_) {
+            for (int i = 0; i < n; i++) if (fl[i]->kind == F_RTAG) { fl[i]->rtag_host_call = true; fl[i]->rtag_dev_base = dev; fl[i]->rtag_host_base = (const uint8_t *) host; }
+        }
+        ~RtagScope() { for (int i = 0; i < n; i++) if (fl[i]->kind == F_RTAG) { fl[i]->rtag_host_call = false; fl[i]->rtag_dev_base = nullptr; fl[i]->rtag_host_base = nullptr; } }
+    } rtag_scope(filters, nfilters, f->h_in_data.p, data);
     {
         PhaseScope ph(HP_CHAIN);
         const int cr = chain_dev(filters, nfilters, &in, &out, garbage, stats);

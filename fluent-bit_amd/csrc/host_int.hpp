@@ -92,6 +92,17 @@ int simulate_fx4(const std::vector<uint8_t> &b, const DevFx &fx, int ncap, const
 bool parse_ra(const char *pat, DevKey &k, std::string &why);
 // flb_slist_split_tokens(list, str, max) (src/flb_slist.c:182-217; recmod.cpp): `max` tokens, then the rest of the line as one more entry
 void slist_split_tokens(const std::string &s, int max, std::vector<std::string> &out);
+// flb_ra_create(text, FLB_FALSE): the parts ra_parse_buffer cuts a record accessor's text into (src/flb_record_accessor.c:74-230;
+// typeconv.cpp).  RA_SPLIT_SKIP: a `$key...` part the accessor's grammar refuses (flb_ra_create answers NULL); RA_SPLIT_REFUSE: a part
+// this project's limits refuse (`why` says which)
+enum { RA_STR = 0, RA_TAG = 1, RA_TAGPART = 2, RA_REGEX = 3, RA_KEY = 4 };
+enum { RA_SPLIT_OK = 0, RA_SPLIT_SKIP = 2, RA_SPLIT_REFUSE = 3 };
+struct RaPart {
+    int kind = RA_STR, id = 0;          // id: the regex id of `$n` / the part of `$TAG[n]`
+    std::string str;                    // RA_STR: the text
+    DevKey key = {};                    // RA_KEY
+};
+int ra_split(const std::string &a, std::vector<RaPart> &parts, std::string &why);
 // "<field> <regex>" rule of filter_grep / filter_log_to_metrics -> device rule (tables uploaded into blobs)
 bool compile_rule(const std::string &ra_field, const char *pattern, GrepRule &r, std::vector<TableBlob *> &blobs, std::string &why, bool *nonregular = nullptr);
 
@@ -141,7 +152,7 @@ uint64_t l2m_limbs_bits(const uint64_t *limbs, uint64_t n_nan, uint64_t n_pinf, 
 struct KernelProf { const char *name; double ms = 0; uint64_t launches = 0; };
 struct ProfPending { const char *name; hipEvent_t e0, e1; };
 
-enum { F_PARSER = 1, F_GREP = 2, F_L2M = 3, F_JSONFMT = 4, F_MODIFY = 5, F_RECMOD = 6, F_NEST = 7, F_TYPECONV = 8 };
+enum { F_PARSER = 1, F_GREP = 2, F_L2M = 3, F_JSONFMT = 4, F_MODIFY = 5, F_RECMOD = 6, F_NEST = 7, F_TYPECONV = 8, F_RTAG = 9 };
 
 struct ModState;                 // filter_modify's program and buffers (modify.cpp)
 void mod_state_destroy(ModState *);
@@ -151,6 +162,8 @@ struct NestState;                // filter_nest's program and buffers (nest.cpp)
 void nest_state_destroy(NestState *);
 struct TypeconvState;            // filter_type_converter's program and buffers (typeconv.cpp)
 void typeconv_state_destroy(TypeconvState *);
+struct RtagState;                // filter_rewrite_tag's program, buffers and last emissions (rtag.cpp)
+void rtag_state_destroy(RtagState *);
 
 struct flbgpu_filter {
     int kind = 0;
@@ -222,6 +235,12 @@ struct flbgpu_filter {
     NestState *nest = nullptr;
     // filter_type_converter
     TypeconvState *typeconv = nullptr;
+    // filter_rewrite_tag; during a host-level call (flbgpu_filter_chain_run): the emitter's callback is asked, and the chunk at
+    // rtag_dev_base is the caller's buffer at rtag_host_base
+    RtagState *rtag = nullptr;
+    bool rtag_host_call = false;
+    const void *rtag_dev_base = nullptr;
+    const uint8_t *rtag_host_base = nullptr;
     bool host_list = false;                     // filter_parser: a list of several parsers with host parsers in it (flbgpu.cpp host_list_rx)
     flbgpu::DevBuf d_hres[flbgpu::MAX_HOST_PARSERS];   // their answers for the chunk at hand
     // msgpack -> JSON output formatter (packfmt.cpp)
@@ -246,6 +265,7 @@ struct flbgpu_filter {
         recmod_state_destroy(recmod);
         nest_state_destroy(nest);
         typeconv_state_destroy(typeconv);
+        rtag_state_destroy(rtag);
         for (auto *b : rule_blobs) delete b;
         for (auto *b : host_rx) if (b) rx::bt_free(b);
         delete l2m_gate;
@@ -300,6 +320,9 @@ bool run_nest_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk
 
 // filter_type_converter entry (typeconv.cpp)
 bool run_typeconv_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
+
+// filter_rewrite_tag entry (rtag.cpp)
+bool run_rtag_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
 
 // filter_log_to_metrics entry used by flbgpu_filter_run / flbgpu_filter_run_dev
 bool run_l2m_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, hipStream_t st, int *ret);

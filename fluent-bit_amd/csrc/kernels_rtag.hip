@@ -1,17 +1,17 @@
-// kernels_typeconv.hip -- filter_type_converter, a lane per record (typeconv_kernels.inc; shares kdev.inc with the other kernel units)
+// kernels_rtag.hip -- filter_rewrite_tag, a lane per record (rtag_kernels.inc; shares kdev.inc with the other kernel units)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 #include <type_traits>
 #include "dev.hpp"
 #include "numconv.hpp"
-#include "typeconv.hpp"
+#include "rtag.hpp"
 
 namespace flbgpu {
 
 #include "kdev.inc"
-#include "canon_walk.inc"
 #include "ra_lds.inc"
-#include "typeconv_kernels.inc"
+#include "fmt_dev.inc"
+#include "rtag_kernels.inc"
 
 }  // namespace flbgpu

@@ -2245,7 +2245,9 @@ void make_ascii_stub(TableSet &t, bool want_capture) {
 
 }  // namespace
 
-bool compile(const char *pattern, size_t len, unsigned options, bool want_captures, Program &out, std::string &err) {
+namespace {
+// numbered: nullptr = the caps row holds the NAMED groups (filter_parser); else bit g = group g's span goes to columns 2g, 2g + 1
+bool compile_with(const char *pattern, size_t len, unsigned options, bool want_captures, const uint32_t *numbered, Program &out, std::string &err) {
     Syntax sx;
     sx.s = sx.p = (const unsigned char *) pattern;
     sx.e = sx.s + len;
@@ -2277,7 +2279,11 @@ bool compile(const char *pattern, size_t len, unsigned options, bool want_captur
     out.name_groups = sx.name_groups;
     // caps row layout: one (begin, end) pair per (name, group) in onig_foreach_name order
     out.slot2cap.assign(2 * (size_t) (sx.ncap + 1), 0xFF);
-    {
+    if (numbered) {
+        for (int g = 1; g <= sx.ncap && g < 31; g++)
+            if ((*numbered >> g) & 1u) { out.slot2cap[2 * g] = (uint8_t) (2 * g); out.slot2cap[2 * g + 1] = (uint8_t) (2 * g + 1); }
+    }
+    else {
         int f = 0;
         for (size_t i = 0; i < sx.names.size(); i++)
             for (int g : sx.name_groups[i]) {
@@ -2316,6 +2322,15 @@ bool compile(const char *pattern, size_t len, unsigned options, bool want_captur
     out.why_nfa = why;
     if (!ascii_ok) { make_ascii_stub(out.ascii, want_captures); out.ascii_stub = true; }
     return true;
+}
+}  // namespace
+
+bool compile(const char *pattern, size_t len, unsigned options, bool want_captures, Program &out, std::string &err) {
+    return compile_with(pattern, len, options, want_captures, nullptr, out, err);
+}
+
+bool compile_numbered(const char *pattern, size_t len, unsigned options, uint32_t group_mask, Program &out, std::string &err) {
+    return compile_with(pattern, len, options, true, &group_mask, out, err);
 }
 
 // ---------------------------------------------------------------- the optimizer-dependent corners: which texts can meet them

@@ -195,6 +195,11 @@ bool corner(unsigned flags, const uint8_t *s, int len);
 bool compile(const char *pattern, size_t len, unsigned options, bool want_captures, Program &out,
              std::string &err);
 
+// The capture program with the spans addressed by group NUMBER (filter_rewrite_tag's `$1` .. `$9`): slot2cap sends group g of
+// group_mask (bit g, g >= 1) to columns 2g, 2g + 1 of the caps row and every other group nowhere.  Group 0 has no open slot: its span is
+// [the start the reverse pass found, the end the forward walk answers].  compile() itself is unchanged: the named-field layout.
+bool compile_numbered(const char *pattern, size_t len, unsigned options, uint32_t group_mask, Program &out, std::string &err);
+
 // src/flb_regex.c:60-152: "/pat/imx" option syntax.  Returns the inner pattern range and options.
 void split_flb_pattern(const char *pattern, const char **start, const char **end, unsigned *options);
 

@@ -34,70 +34,25 @@ int type_of_word(const std::string &w) {
 
 enum { ACC_KEY = 0, ACC_INERT = 1, ACC_SKIP = 2, ACC_REFUSE = 3 };
 
-// flb_ra_create(from_key, FLB_FALSE) as ra_parse_buffer cuts the text into parts (src/flb_record_accessor.c:74-230), then
-// get_ra_parser (:767-779): the FIRST part decides, and only a part with a key finds anything.  ACC_SKIP: a `$key...` part the
-// accessor's grammar refuses -- flb_ra_create answers NULL.
+// get_ra_parser (src/flb_record_accessor.c:767-779) over the parts ra_split cuts: the FIRST part decides, and only a part with a key
+// finds anything -- a `$key...` part, or the plain text in front of the first '$', which the accessor keeps as a key of that name.
+// ACC_SKIP: a `$key...` part the accessor's grammar refuses -- flb_ra_create answers NULL.
 int accessor(const std::string &a, DevKey &key, std::string &why) {
-    const long len = (long) a.size();
-    int first = -1;                 // -1 none yet, 0 a part without a key, 1 a key (in `key`)
-    DevKey tmp;
-    auto string_part = [&](long from, long to) {
-        if (first >= 0) return true;
-        if (to - from >= MAX_KEY) { why = "from_key '" + a + "': key longer than " + std::to_string(MAX_KEY - 1) + " bytes"; return false; }
-        memset(&key, 0, sizeof(key));
-        key.is_ra = 1;
-        memcpy(key.key, a.data() + from, (size_t) (to - from));
-        key.key_len = (int) (to - from);
-        first = 1;
-        return true;
-    };
-    long pre = 0, end = 0, i;
-    for (i = 0; i < len; i++) {
-        if (a[i] != '$') continue;
-        if (i > pre && !string_part(pre, i)) return ACC_REFUSE;
-        pre = i;
-        const long n = i + 1;
-        if (n >= len) break;
-        if (isdigit((unsigned char) a[n])) {                             // $0 .. $9: a regex id
-            if (first < 0) first = 0;
-            i++;
-            pre = i + 1;
-            continue;
-        }
-        if (n + 2 < len && !a.compare(n, 3, "TAG")) {                    // $TAG, $TAG[n]
-            if (first < 0) first = 0;
-            if (n + 4 < len && a[n + 3] == '[') {
-                const long t = n + 3;
-                const size_t close = a.find(']', t);
-                long e = close == std::string::npos ? -1 : (long) close - t;
-                if (e == 0) e = -1;
-                i = t + e + 1;
-                pre = i;
-                continue;
-            }
-            i = n + 3;
-            pre = n + 3;
-            continue;
-        }
-        int quotes = 0;
-        for (end = i + 1; end < len; end++) {
-            const char c = a[end];
-            if (c == '\'') quotes++;
-            else if (c == '.' && (quotes & 1)) continue;
-            else if (c == '.' || c == ' ' || c == ',' || c == '"') break;
-        }
-        std::string w2;
-        if (!parse_ra(a.substr(i, end - i).c_str(), tmp, w2)) {
-            if (w2 == "unterminated subkey string" || w2 == "bad subkey" || w2 == "trailing characters in record accessor") return ACC_SKIP;
-            why = "from_key '" + a + "': " + w2;
-            return ACC_REFUSE;
-        }
-        if (first < 0) { key = tmp; first = 1; }
-        pre = end;
-        i = end;
+    std::vector<RaPart> parts;
+    const int rc = ra_split(a, parts, why);
+    if (!parts.empty() && parts[0].kind == RA_STR && parts[0].str.size() >= (size_t) MAX_KEY) {
+        why = "from_key '" + a + "': key longer than " + std::to_string(MAX_KEY - 1) + " bytes";
+        return ACC_REFUSE;
     }
-    if ((i - 1 > end && pre < i) || i == 1) { if (pre < len && !string_part(pre, len)) return ACC_REFUSE; }
-    return first == 1 ? ACC_KEY : ACC_INERT;
+    if (rc == RA_SPLIT_SKIP) return ACC_SKIP;
+    if (rc == RA_SPLIT_REFUSE) { why = "from_key '" + a + "': " + why; return ACC_REFUSE; }
+    if (parts.empty() || (parts[0].kind != RA_STR && parts[0].kind != RA_KEY)) return ACC_INERT;
+    if (parts[0].kind == RA_KEY) { key = parts[0].key; return ACC_KEY; }
+    memset(&key, 0, sizeof(key));
+    key.is_ra = 1;
+    memcpy(key.key, parts[0].str.data(), parts[0].str.size());
+    key.key_len = (int) parts[0].str.size();
+    return ACC_KEY;
 }
 
 size_t pad4(size_t n) { return (n + 3) & ~(size_t) 3; }
@@ -211,6 +166,78 @@ std::string describe(const TProgram &pg) {
 }
 
 }  // namespace
+
+// flb_ra_create(text, FLB_FALSE) as ra_parse_buffer cuts the text into parts (src/flb_record_accessor.c:74-230), in order
+int flbgpu::ra_split(const std::string &a, std::vector<RaPart> &parts, std::string &why) {
+    const long len = (long) a.size();
+    auto string_part = [&](long from, long to) {
+        RaPart p;
+        p.kind = RA_STR;
+        p.str = a.substr((size_t) from, (size_t) (to - from));
+        parts.push_back(p);
+    };
+    long pre = 0, end = 0, i;
+    for (i = 0; i < len; i++) {
+        if (a[i] != '$') continue;
+        if (i > pre) string_part(pre, i);
+        pre = i;
+        const long n = i + 1;
+        if (n >= len) break;
+        if (isdigit((unsigned char) a[n])) {                             // $0 .. $9: a regex id (atoi reads on, one digit is consumed)
+            RaPart p;
+            p.kind = RA_REGEX;
+            p.id = atoi(a.c_str() + n);
+            parts.push_back(p);
+            i++;
+            pre = i + 1;
+            continue;
+        }
+        if (n + 2 < len && !a.compare(n, 3, "TAG")) {                    // $TAG, $TAG[n]
+            if (n + 4 < len) {
+                end = -1;
+                if (a[n + 3] == '[') {
+                    const long t = n + 3;
+                    const size_t close = a.find(']', t);
+                    end = close == std::string::npos ? -1 : (long) close - t;
+                    if (end == 0) end = -1;
+                    RaPart p;
+                    p.kind = RA_TAGPART;
+                    p.id = atoi(a.c_str() + t + 1);
+                    parts.push_back(p);
+                    i = t + end + 1;
+                    pre = i;
+                    continue;
+                }
+            }
+            RaPart p;
+            p.kind = RA_TAG;
+            parts.push_back(p);
+            i = n + 3;
+            pre = n + 3;
+            continue;
+        }
+        int quotes = 0;
+        for (end = i + 1; end < len; end++) {
+            const char c = a[end];
+            if (c == '\'') quotes++;
+            else if (c == '.' && (quotes & 1)) continue;
+            else if (c == '.' || c == ' ' || c == ',' || c == '"') break;
+        }
+        RaPart p;
+        p.kind = RA_KEY;
+        std::string w2;
+        if (!parse_ra(a.substr(i, end - i).c_str(), p.key, w2)) {
+            if (w2 == "unterminated subkey string" || w2 == "bad subkey" || w2 == "trailing characters in record accessor") return RA_SPLIT_SKIP;
+            why = w2;
+            return RA_SPLIT_REFUSE;
+        }
+        parts.push_back(p);
+        pre = end;
+        i = end;
+    }
+    if ((i - 1 > end && pre < i) || i == 1) { if (pre < len) string_part(pre, len); }
+    return RA_SPLIT_OK;
+}
 
 struct TypeconvState {
     int nrules = 0;

@@ -5,7 +5,7 @@
 // original entries go out as rm_walk / mp_canon re-pack them (runs of already-canonical entries as one span); behind them, for every
 // rule whose key the ORIGINAL body holds, to_key and the converted value -- or the value as it was when the conversion fails.
 // Nested values are never interpreted, only walked; the numbers come from numconv.hpp and write straight into the sink.
-// Included inside namespace flbgpu after kdev.inc and canon_walk.inc (rm_walk, RM_MAP_HDR).
+// Included inside namespace flbgpu after kdev.inc, canon_walk.inc (rm_walk, RM_MAP_HDR) and ra_lds.inc (the key lookup).
 
 struct TcTable {
     const LDS_AS uint32_t *w;       // the table's words in LDS
@@ -55,69 +55,12 @@ template <class S> DEV void tc_put_lds(S &s, const LDS_AS uint32_t *e, uint32_t 
     for (uint32_t j = 0; j < L; j++) s.put((e[j >> 2] >> (8 * (j & 3))) & 0xffu);
 }
 
-// are the L bytes at key (all of them inside the record: mp_tok checked the payload) the entry at e?  A 4-byte load is issued
-// only where 4 bytes remain inside the key.
-DEV bool tc_eq(const LDS_AS uint32_t *e, uint32_t L, const uint8_t *key) {
-    uint32_t j = 0;
-    bool eq = true;
-    for (; eq && j + 4 <= L; j += 4) eq = ldu32(key + j) == e[j >> 2];
-    for (; eq && j < L; j++) eq = ld8(key + j) == ((e[j >> 2] >> (8 * (j & 3))) & 0xffu);
-    return eq;
-}
-
-// ra_key_val_id (src/flb_ra_key.c:108-135): the value of the LAST entry of the map at `map` whose key is a STR equal to the name
-DEV const uint8_t *tc_find_last(const uint8_t *map, const uint8_t *end, const LDS_AS uint32_t *name, uint32_t nlen) {
-    Tok m = mp_tok(map, end);
-    if (m.type != T_MAP) return nullptr;
-    const uint8_t *p = m.next, *found = nullptr;
-    for (uint32_t i = 0; i < m.len; i++) {
-        Tok k = mp_tok(p, end);
-        const uint8_t *v = mp_end_of(k, p, end, 2);
-        if (!v) return nullptr;
-        if (k.type == T_STR && k.len == nlen && tc_eq(name, nlen, k.next)) found = v;
-        p = mp_end_of(mp_tok(v, end), v, end, 2);
-        if (!p) return nullptr;
-    }
-    return found;
-}
-
-// flb_ra_get_kv_pair (src/flb_record_accessor.c:788-801, src/flb_ra_key.c:151-236, 374-434) on the original body: the top-level
-// entry, then the sub-keys when its value is a map or an array (any other value is taken as it is).  A path that ends on an array
-// index has no key object, and the filter reads that as "not found" (type_converter.c:277-281).
+// flb_ra_get_kv_pair (src/flb_record_accessor.c:788-801, src/flb_ra_key.c:151-236, 374-434) on the original body (ra_lds.inc).  A
+// path that ends on an array index has no key object, and the filter reads that as "not found" (type_converter.c:277-281).
 DEV const uint8_t *tc_lookup(const TcTable &tb, int ri, const uint8_t *body, const uint8_t *end) {
     const LDS_AS uint32_t *r = tb.w + TC_RULE_WORDS * (uint32_t) ri;
     if (r[0] & TC_INERT) return nullptr;
-    const uint8_t *val = tc_find_last(body, end, tb.w + (r[2] >> 2), r[1]);
-    if (!val) return nullptr;
-    const uint32_t nsub = (r[0] >> 16) & 0xffu;
-    Tok t = mp_tok(val, end);
-    if ((t.type != T_MAP && t.type != T_ARRAY) || nsub == 0) return val;
-    const LDS_AS uint32_t *sub = tb.w + (r[5] >> 2);
-    const uint8_t *cur = val;
-    uint32_t matched = 0;
-    bool last_index = false;
-    for (uint32_t s = 0; s < nsub; s++) {
-        Tok c = mp_tok(cur, end);
-        const uint32_t s0 = sub[2 * s];
-        if (s0 & TC_SUB_INDEX) {
-            const uint32_t idx = s0 & ~TC_SUB_INDEX;
-            if (c.type != T_ARRAY || idx >= c.len) return nullptr;
-            const uint8_t *p = c.next;
-            for (uint32_t i = 0; i < idx; i++) { p = mp_skip(p, end); if (!p) return nullptr; }
-            cur = p;
-            last_index = true;
-            if (++matched == nsub) break;
-            continue;
-        }
-        if (c.type != T_MAP) break;
-        const uint8_t *v = tc_find_last(cur, end, tb.w + (sub[2 * s + 1] >> 2), s0);
-        if (!v) continue;                          // "try next entry": the levels are never completed
-        cur = v;
-        last_index = false;
-        if (++matched == nsub) break;
-    }
-    if (matched != nsub || last_index) return nullptr;
-    return cur;
+    return ra_lds_path(tb.w, tb.w + (r[2] >> 2), r[1], tb.w + (r[5] >> 2), (r[0] >> 16) & 0xffu, body, end, false);
 }
 
 struct TcSrc {

@@ -246,6 +246,81 @@ int flbgpu_type_converter_parse_check(int nprops, const char *const *names, cons
  * length (always 0; the emit pass never stores outside a row's room, and a call that counts one answers NOTOUCH) */
 void flbgpu_type_converter_counters(flbgpu_filter *f, uint64_t out[4]);
 
+/* ---- filter_rewrite_tag: replaces cb_rewrite_tag_init / cb_rewrite_tag_filter / cb_rewrite_tag_exit ----
+ * plugins/filter_rewrite_tag/rewrite_tag.c:112-190 (process_config, behind the config map of :590-613), 356-423 (process_record),
+ * 425-557 (one call); src/flb_record_accessor.c:74-230 (the parts of an accessor), 456-619 (ra_translate_*), 644-699
+ * (flb_ra_translate_check), 753-764 (flb_ra_regex_match); src/flb_ra_key.c:31- (msgpack_object_to_ra_value), 108-135
+ * (ra_key_val_id), 151-236 (subkey_to_object), 374- (flb_ra_key_regex_match).  (names[i], values[i]) are the instance's properties
+ * in configuration order, names without case:
+ *   rule           "KEY REGEX NEW_TAG KEEP", split as flb_slist_split_tokens(.., 4) splits (quotes allowed); may repeat, the rules run
+ *                  in configuration order.  Fewer than four entries fail the config map and are refused; what follows the fourth
+ *                  token is a fifth entry nobody reads.  KEEP is flb_utils_bool: true / on / yes without case keep the record,
+ *                  every other word does not.
+ *   emitter_name, emitter_mem_buf_limit   accepted and not looked at (there is no emitter instance here: see set_emitter)
+ *   emitter_storage.type                  "memory" or "filesystem" without case, anything else is refused (:281-286)
+ * No rule at all starts (the reference warns, :184-187) and every call answers NOTOUCH.
+ * KEY: flb_ra_regex_match reads the FIRST part of the accessor.  `$key`, `$key['a'][1]` and a plain name (the accessor keeps the text
+ * in front of the first '$' as a key of that name) look the LAST STR key of that name up in the body, then the sub-keys through maps
+ * and arrays (on a scalar they are ignored); `$TAG`, `$TAG[n]` and `$0`..`$9` never match.  Only a STR value is matched: flb_regex_do,
+ * a search.  The first rule that matches wins.
+ * NEW_TAG is composed part by part (flb_ra_translate): literal text; `$TAG` the call's tag; `$TAG[n]` its n-th dot-separated part (a
+ * tag without dots answers only `$TAG[0]`); `$0`..`$9` the capture by NUMBER -- nothing for an unset or absent group, nothing at all
+ * for a pattern without groups (flb_regex_do frees the region when num_regs is 1), named groups switch the numbering of unnamed ones
+ * off; `$key...` the value as text: STR its bytes, integers "%ld" of via.i64 (a uint64 above 2^63-1 prints negative), float32 /
+ * float64 "%f" through a 32-byte buffer (a text of 31 characters and more leaves 30 of them and the NUL behind them in the tag), bool
+ * true / false, nil null, BIN lower-case hex, a MAP its JSON (flb_msgpack_to_json_str, escape_unicode on); arrays, ext values and
+ * missing keys add nothing.  An empty result is a tag.
+ * Refused, NULL + last_error: an unknown property, fewer than four entries, a bad storage type, a KEY or NEW_TAG the record accessor
+ * refuses, a pattern that does not compile -- and, although the reference accepts them: a pattern that is not a regular expression
+ * (look-around, back-references, atomic groups ...; last_error says so), more than 32 rules, a NEW_TAG of more than 16 parts, a rule
+ * table of more than 24576 bytes (it sits in LDS), a key name of 128 bytes or more, more than 8 sub-keys or 256 bytes of sub-key
+ * names, a `$name` that does not start with a letter or '_', `$n` with n > 9 where the pattern has a group n (atoi reads `$12` as group 12; without such a group the part
+ * adds nothing), more than 31 capture groups next to a NEW_TAG with a `$n`, and an empty KEY (the reference reads the head of an empty list).
+ * One call (:425-557): a matched record goes to the emitter with the bytes from the end of the previously RETURNED record to its own
+ * end (data + pre: what the decoder skipped in front of it, group markers, travels with it).  A record goes to the output
+ * (emit_raw_record: its own bytes) when no rule matched, when its rule says keep, or when the emitter refused it (:417-420).  With no
+ * accepted emission the call answers NOTOUCH; otherwise MODIFIED, possibly with 0 bytes -- and NOTOUCH when the decoder's loop did not
+ * end on a clean end of data (:533-551), although the emissions made in front of the error stand.  Runs through
+ * flbgpu_filter_run[_dev], flbgpu_filter_chain_run[_dev] (the MODIFIED output feeds the next filter; every instance keeps its own
+ * emitted list), flbgpu_filter_last_counts (records decoded / records kept) and flbgpu_filter_destroy. */
+flbgpu_filter *flbgpu_filter_rewrite_tag_create(int nprops, const char *const *names, const char *const *values);
+/* host only, no device: the rules as one line of text --
+ * "K<hex name>{.<hex sub-key>|[<index>]}...|-,P<hex pattern>,[<part> <part> ...],<keep|drop>;..." ("-": the rule never matches) with the
+ * parts of NEW_TAG by kind: S<hex text>, T ($TAG), t<n> ($TAG[n]), R<n> ($n), K<hex name>... ($key...) -- 0, or -1 + last_error where
+ * create refuses */
+int flbgpu_rewrite_tag_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap);
+/* the tag of the following calls (cb_filter's tag / tag_len); the default is the empty tag */
+void flbgpu_rewrite_tag_set_tag(flbgpu_filter *f, const char *tag, int tag_len);
+/* stands where in_emitter_add_record stands (:407).  Called by the host-level flbgpu_filter_run / flbgpu_filter_chain_run once per
+ * emission, in record order, with buf inside the caller's input (inside a filter-owned copy of the instance's input when it runs
+ * behind another filter of a chain).  An answer < 0 keeps that record and does not count it.  Without a callback every emission is
+ * accepted.  The device-level calls (_dev) ask nobody and accept every emission. */
+void flbgpu_rewrite_tag_set_emitter(flbgpu_filter *f, int (*emit)(void *ctx, const char *tag, int tag_len, const void *buf, size_t size), void *ctx);
+/* the last call's emissions, in record order: recs[i] = bytes [in_off, in_off + len) of the instance's input chunk under the tag
+ * tags[tag_off .. tag_off + tag_len).  flbgpu_rewrite_tag_emitted answers host pointers and lists the emissions the emitter took;
+ * input is the caller's buffer after a host-level call (a filter-owned copy behind another filter of a chain) and NULL after a
+ * device-level one.  The _dev twin answers the same three things as device pointers after flbgpu_filter_run_dev (input stays NULL:
+ * the offsets index the chunk the caller passed).  The storage is filter-owned and valid until the next call on this filter or its
+ * destruction.  0, or -1 + last_error. */
+typedef struct flbgpu_rtag_emitted_rec {
+    uint64_t in_off, tag_off;
+    uint32_t len, tag_len;
+} flbgpu_rtag_emitted_rec;
+typedef struct flbgpu_rtag_emitted {
+    uint64_t count;
+    const flbgpu_rtag_emitted_rec *recs;
+    const char *tags;
+    uint64_t tag_bytes;
+    const uint8_t *input;
+    uint64_t input_bytes;
+} flbgpu_rtag_emitted;
+int flbgpu_rewrite_tag_emitted(flbgpu_filter *f, flbgpu_rtag_emitted *out);
+int flbgpu_rewrite_tag_emitted_dev(flbgpu_filter *f, flbgpu_rtag_emitted *out);
+/* since the filter was created: out[0] records emitted (the emit_records metric), out[1] emissions the callback refused, out[2] rows
+ * whose tag was written with another length than it was sized with or whose capture walk failed (always 0; the emit pass never stores
+ * outside a row's room of the tag arena, and a call that counts one answers NOTOUCH), out[3] tag bytes written */
+void flbgpu_rewrite_tag_counters(flbgpu_filter *f, uint64_t out[4]);
+
 /* ---- filter_log_to_metrics: replaces cb_log_to_metrics_init / cb_log_to_metrics_filter -----------
  * plugins/filter_log_to_metrics/log_to_metrics.c:655-968,970-1156.  (keys[i], values[i]) are the
  * instance's properties in configuration order; the ones read are regex / exclude (set_rules
