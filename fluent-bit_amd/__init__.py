@@ -691,6 +691,56 @@ class MultilineStream:
             self.h = None
 
 
+def _ml_defs(parsers):
+    """(n, names array, handles array) of a {name: MultilineParser} dictionary, as flbgpu_filter_multiline_create takes them"""
+    items = list((parsers or {}).items())
+    names = (c_char_p * max(len(items), 1))(*[_b(k) for k, _ in items])
+    hs = (c_void_p * max(len(items), 1))(*[v.h if v is not None else None for _, v in items])
+    return len(items), names, hs
+
+
+class FilterMultiline(_Filter):
+    """filter_multiline, mode parser with buffer off (plugins/filter_multiline/ml.c): props = [(name, value), ...] in configuration
+    order, e.g. [("multiline.parser", "java"), ("multiline.key_content", "log"), ("buffer", "off")]; parsers: the [MULTILINE_PARSER]
+    definitions the configuration knows, {name: MultilineParser} (java, go, python and ruby are built in).  filter() answers -1 for a
+    chunk it hands back (a record with a non-empty metadata map, a record with an empty text that starts a group)."""
+
+    def __init__(self, props, parsers=None):
+        L = lib()
+        L.flbgpu_filter_multiline_create.restype = c_void_p
+        self.parsers = dict(parsers or {})                     # (kept alive: the library borrows them)
+        n, names, hs = _ml_defs(self.parsers)
+        L.flbgpu_filter_multiline_create.argtypes = [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p]
+        pn, pk, pv = _props(props)
+        self.h = L.flbgpu_filter_multiline_create(pn, pk, pv, n, names, hs)
+        if not self.h:
+            raise ValueError("flbgpu_filter_multiline_create: " + last_error())
+
+    def counters(self):
+        """(records that returned OK, truncations, calls handed back with -1, size/emit mismatches) since the filter was created"""
+        o = (c_uint64 * 4)()
+        lib().flbgpu_multiline_counters.argtypes = [c_void_p, c_void_p]
+        lib().flbgpu_multiline_counters(self.h, o)
+        return tuple(int(x) for x in o)
+
+    def state(self):
+        """rule_to_state of the stream: -1 none, else the rule's index"""
+        lib().flbgpu_multiline_state.argtypes = [c_void_p]
+        return int(lib().flbgpu_multiline_state(self.h))
+
+
+def multiline_parse_check(props, parsers=None):
+    """what FilterMultiline keeps of props as one line of text (host only); raises ValueError where create refuses.  parsers:
+    {name: MultilineParser | None} -- a name without a definition still counts as defined (the definitions live on the device)"""
+    buf = ctypes.create_string_buffer(1 << 12)
+    n, names, hs = _ml_defs(parsers)
+    lib().flbgpu_multiline_parse_check.argtypes = [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t]
+    pn, pk, pv = _props(props)
+    if lib().flbgpu_multiline_parse_check(pn, pk, pv, n, names, hs, buf, len(buf)) != 0:
+        raise ValueError(last_error())
+    return buf.value.decode()
+
+
 class MultilineList:
     """several multiline parsers on one tailed file -- in_tail's `multiline.parser docker, cri` (flb_ml_append_text's loop over the parser
     instances, src/multiline/flb_ml.c:671-760).  `parsers`: MultilineParser objects in configuration order, each with a parser in front.

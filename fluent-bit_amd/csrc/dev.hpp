@@ -807,6 +807,41 @@ void launch_ml_rows(const MlArgs &a, uint64_t *row_off, hipStream_t st);
 void launch_ml_emit(const MlArgs &a, int cus, hipStream_t st);
 void launch_ml_carry(const MlArgs &a, hipStream_t st);
 
+// ---- filter_multiline, mode parser with buffer off (mlfilter_kernels.inc; plugins/filter_multiline/ml.c:839-909): the records of a chunk
+// are the items of the multiline core above -- item k >= 1 is the k-th record the decoder hands out, its text the STR value under
+// key_content, item 0 the (always empty) carried buffer.  k_ml_match / k_ml_fscan_* / k_ml_act / k_ml_ghead / k_ml_trunc / k_ml_override run
+// on them unchanged; what a group's record looks like is decided here.
+enum { MLF_RULES = 0, MLF_NOTPROC = 1 };                 // cls[]: handed to the rules / not processed (no content entry, ENDSWITH text too short)
+constexpr uint32_t MLF_NOSLOT = 0xFFFFFFFFu;
+struct MlfWords {                                        // device words of one call
+    unsigned long long first_bad, meta_refused, truncated, mismatch, empty_start, big;
+    unsigned int last_sec, last_nsec, has_reg, pad;
+};
+struct MlfArgs {
+    const uint8_t *data; const uint64_t *row_off; uint64_t n, bytes;          // the chunk's rows
+    uint32_t regex, type, match_len, has_key, key_len;
+    uint8_t key[256];                                    // key_content, raw
+    uint32_t *keep; const uint64_t *koff;                // [n] rows the decoder hands out, their scan
+    uint64_t N;                                          // items, the carried buffer included
+    uint64_t *ls; uint32_t *ll;                          // [N] the item's text: offset into data, length (MlArgs.ls / ll)
+    uint32_t *irow; uint8_t *cls; uint32_t *tsec, *tnsec;// [N] row, MLF_*, the record's time
+    uint32_t *info; uint64_t *F;                         // [N] MlArgs.info / F (k_mlf_fix rewrites them for MLF_NOTPROC items)
+    const uint8_t *act; const uint32_t *c; const uint64_t *coff; const uint32_t *head; const uint64_t *gidx; const uint64_t *ghead;
+    uint32_t *ev; const uint64_t *evoff; uint32_t *regidx;  // [2N] registrations of a time (flb_ml_register_context): slot 2k before item k's own flush, 2k + 1 behind it
+    uint32_t *plen; const uint64_t *po;                  // [N] bytes charged to the item (a group's record to its first item), their scan
+    uint32_t *pre, *dup, *nrec; const uint64_t *ridx;    // [N] offset of the concatenation inside the record / bytes of the seed's own record / records, their scan
+    uint32_t carry_sec, carry_nsec;                      // the time registered last in an earlier call
+    uint8_t *out; uint64_t *rows_out;
+    MlfWords *w;
+};
+void launch_mlf_class(const MlfArgs &a, hipStream_t st);
+void launch_mlf_items(const MlfArgs &a, hipStream_t st);
+void launch_mlf_fix(const MlfArgs &a, hipStream_t st);
+void launch_mlf_plan(const MlfArgs &a, hipStream_t st);
+void launch_mlf_regidx(const MlfArgs &a, hipStream_t st);
+void launch_mlf_size(const MlfArgs &a, hipStream_t st);
+void launch_mlf_emit(const MlfArgs &a, hipStream_t st);
+
 struct GatherArgs {
     const uint8_t *data;
     const uint64_t *row_off;

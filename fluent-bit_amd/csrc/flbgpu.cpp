@@ -2382,6 +2382,7 @@ static int run_any_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_
     else if (f->kind == F_NEST) ok = run_nest_dev(f, in, out, st, &ret, garbage);
     else if (f->kind == F_TYPECONV) ok = run_typeconv_dev(f, in, out, st, &ret, garbage);
     else if (f->kind == F_RTAG) ok = run_rtag_dev(f, in, out, st, &ret, garbage);
+    else if (f->kind == F_MLFILTER) ok = run_mlfilter_dev(f, in, out, st, &ret, garbage);
     else ok = f->kind == F_PARSER ? run_parser_dev(f, in, out, st, &ret) : run_grep_dev(f, in, out, st, &ret, garbage);
     if (!ok) return FLBGPU_FILTER_NOTOUCH;      // errors degrade to NOTOUCH (SURVEY 8b "Errors")
     return ret;
@@ -2562,7 +2563,8 @@ static int chain_dev(flbgpu_filter *const *filters, int n, const flbgpu_dev_chun
             stats[i].out_bytes = ret == FLBGPU_FILTER_MODIFIED ? o.bytes : cur.bytes;
         }
         // (flb_filter_do treats every answer but MODIFIED alike; a single filter's own error code -- record_modifier's -1 -- goes to the caller)
-        if (ret < 0 && n == 1) { *out = cur; return ret; }
+        // filter_multiline's -1 ("this chunk belongs to the CPU plugin, whose stream then owns the rule state") ends a chain of any length
+        if (ret < 0 && (n == 1 || filters[i]->kind == F_MLFILTER)) { *out = cur; return ret; }
         if (ret != FLBGPU_FILTER_MODIFIED) continue;
         modified = true;
         cur = o;

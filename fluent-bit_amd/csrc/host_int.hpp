@@ -152,7 +152,7 @@ uint64_t l2m_limbs_bits(const uint64_t *limbs, uint64_t n_nan, uint64_t n_pinf, 
 struct KernelProf { const char *name; double ms = 0; uint64_t launches = 0; };
 struct ProfPending { const char *name; hipEvent_t e0, e1; };
 
-enum { F_PARSER = 1, F_GREP = 2, F_L2M = 3, F_JSONFMT = 4, F_MODIFY = 5, F_RECMOD = 6, F_NEST = 7, F_TYPECONV = 8, F_RTAG = 9 };
+enum { F_PARSER = 1, F_GREP = 2, F_L2M = 3, F_JSONFMT = 4, F_MODIFY = 5, F_RECMOD = 6, F_NEST = 7, F_TYPECONV = 8, F_RTAG = 9, F_MLFILTER = 10 };
 
 struct ModState;                 // filter_modify's program and buffers (modify.cpp)
 void mod_state_destroy(ModState *);
@@ -164,6 +164,8 @@ struct TypeconvState;            // filter_type_converter's program and buffers 
 void typeconv_state_destroy(TypeconvState *);
 struct RtagState;                // filter_rewrite_tag's program, buffers and last emissions (rtag.cpp)
 void rtag_state_destroy(RtagState *);
+struct MlFilterState;            // filter_multiline's parser, stream state and buffers (mlfilter.cpp)
+void mlfilter_state_destroy(MlFilterState *);
 
 struct flbgpu_filter {
     int kind = 0;
@@ -241,6 +243,8 @@ struct flbgpu_filter {
     bool rtag_host_call = false;
     const void *rtag_dev_base = nullptr;
     const uint8_t *rtag_host_base = nullptr;
+    // filter_multiline (mode parser, buffer off)
+    MlFilterState *mlfilter = nullptr;
     bool host_list = false;                     // filter_parser: a list of several parsers with host parsers in it (flbgpu.cpp host_list_rx)
     flbgpu::DevBuf d_hres[flbgpu::MAX_HOST_PARSERS];   // their answers for the chunk at hand
     // msgpack -> JSON output formatter (packfmt.cpp)
@@ -266,6 +270,7 @@ struct flbgpu_filter {
         nest_state_destroy(nest);
         typeconv_state_destroy(typeconv);
         rtag_state_destroy(rtag);
+        mlfilter_state_destroy(mlfilter);
         for (auto *b : rule_blobs) delete b;
         for (auto *b : host_rx) if (b) rx::bt_free(b);
         delete l2m_gate;
@@ -323,6 +328,9 @@ bool run_typeconv_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_c
 
 // filter_rewrite_tag entry (rtag.cpp)
 bool run_rtag_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
+
+// filter_multiline entry (mlfilter.cpp); *ret may be -1: a record with a non-empty metadata map, the call is handed back
+bool run_mlfilter_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
 
 // filter_log_to_metrics entry used by flbgpu_filter_run / flbgpu_filter_run_dev
 bool run_l2m_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, hipStream_t st, int *ret);

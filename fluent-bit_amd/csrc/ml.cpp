@@ -787,3 +787,17 @@ extern "C" int flbgpu_ml_list_append(flbgpu_ml_list *l, const void *text, size_t
     *out_buf = hb; *out_size = out.bytes;
     return 0;
 }
+
+// ---- what filter_multiline (mlfilter.cpp) reads of a parser: the device side of its definition into `a`, its own key_content ("" none),
+// whether a parser stands in front of it.  False: the parser is not initialised.
+namespace flbgpu {
+bool ml_parser_args(const flbgpu_ml_parser *p, MlArgs &a, std::string &key_content, bool &has_sub, int &nrules) {
+    if (!p || !p->inited) return false;
+    a.p = p->dev; a.rules = p->d_rules.as<GrepRule>();
+    a.prod = p->d_prod.as<uint8_t>(); a.prod_bytes = p->prod_bytes; a.prod_nj = p->prod_nj; a.prod_nS = p->prod_nS; a.prod_T = p->prod_T; a.prod_init = p->prod_init;
+    key_content = p->key_content;
+    has_sub = p->sub != nullptr;
+    nrules = (int) p->src.size();
+    return true;
+}
+}  // namespace flbgpu

@@ -579,6 +579,33 @@ int flbgpu_ml_list_append(flbgpu_ml_list *l, const void *text, size_t bytes, uin
 int flbgpu_ml_list_append_dev(flbgpu_ml_list *l, const void *d_text, uint64_t bytes, uint32_t ts_sec, uint32_t ts_nsec, int skip_empty_lines, int flush,
                               flbgpu_dev_chunk *out, uint64_t *processed, uint64_t *records);
 
+/* ---- filter_multiline, mode parser with buffer off: replaces cb_ml_init / cb_ml_filter ------------------------------------------
+ * plugins/filter_multiline/ml.c:224-446, :839-909, the config map :992-1060; src/multiline/flb_ml.c:763-875 (flb_ml_append_event /
+ * flb_ml_append_object), :1590-1800 (flb_ml_flush_stream_group).  (names[i], values[i]) are the instance's properties in
+ * configuration order: buffer (flb_utils_bool), mode, multiline.parser, multiline.key_content are read; flush_ms, emitter_name,
+ * emitter_storage.type, emitter_mem_buf_limit and debug_flush are accepted and unused; any other name is refused.
+ * (parser_names[i], parsers[i]) are the [MULTILINE_PARSER] definitions the configuration knows (flbgpu_ml_parser_create /
+ * _add_rule / _init); they stay the caller's and must outlive the filter.  java, go, python and ruby are resolved inside.
+ * Refused, with flbgpu_last_error saying which: buffer on (the plugin's default: say `buffer off`), mode partial_message, more than
+ * one name in multiline.parser, a parser with a parser in front (docker, cri), a rule pattern that is not a regular expression (at
+ * flbgpu_ml_parser_add_rule).
+ * The filter runs through flbgpu_filter_run[_dev] / flbgpu_filter_chain_run[_dev]; rule_to_state survives from call to call, the
+ * buffers do not (flb_ml_flush_pending_now).  A call answers -1, counts itself (flbgpu_multiline_counters out[2]) and leaves the stream
+ * and the output alone when a record carries a non-empty metadata map (flb_ml_stream_group_add_metadata's merge is not reproduced) or
+ * when a record with an empty text starts a group (the reference lets the next start join that group).  Such a chunk belongs to the CPU
+ * plugin.  In a chain of several filters the -1 ends the chain and is the chain's answer, whatever the filters in front of it did. */
+flbgpu_filter *flbgpu_filter_multiline_create(int nprops, const char *const *names, const char *const *values, int nparsers,
+                                              const char *const *parser_names, flbgpu_ml_parser *const *parsers);
+/* host only: what create keeps as one line of text ("parser=.. type=.. rules=.. key_content=.. buffer_limit=.."), or -1 where it refuses */
+int flbgpu_multiline_parse_check(int nprops, const char *const *names, const char *const *values, int nparsers, const char *const *parser_names,
+                                 flbgpu_ml_parser *const *parsers, char *desc, size_t cap);
+/* since the filter was created: out[0] records flb_ml_append_event answered OK for (the emit_records metric), out[1] records that
+ * truncated a buffer (emit_truncated), out[2] calls handed back with -1 (metadata, an empty text that starts a group), out[3] records written with another length than they were
+ * sized with (always 0; the emit pass never stores outside a record's room, and a call that counts one fails without an output) */
+void flbgpu_multiline_counters(flbgpu_filter *f, uint64_t out[4]);
+/* rule_to_state of the stream: -1 none, else the rule's index */
+int flbgpu_multiline_state(flbgpu_filter *f);
+
 /* row offsets of an NDJSON buffer (each line with its '\n'); returns the row count or -1 if cap is short */
 int64_t flbgpu_split_lines_host(const void *data, size_t bytes, uint64_t *row_off, size_t cap);
 
