@@ -81,6 +81,11 @@ def lib():
     L.flbgpu_type_converter_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
     L.flbgpu_type_converter_counters.restype = None
     L.flbgpu_type_converter_counters.argtypes = [c_void_p, POINTER(c_uint64)]
+    L.flbgpu_filter_checklist_create.restype = c_void_p
+    L.flbgpu_filter_checklist_create.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p)]
+    L.flbgpu_checklist_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
+    L.flbgpu_checklist_counters.restype = None
+    L.flbgpu_checklist_counters.argtypes = [c_void_p, POINTER(c_uint64)]
     L.flbgpu_filter_rewrite_tag_create.restype = c_void_p
     L.flbgpu_filter_rewrite_tag_create.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p)]
     L.flbgpu_rewrite_tag_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
@@ -423,6 +428,31 @@ def type_converter_parse_check(props):
     """the rules configure() keeps from props, in its order, as one line of text (host only); raises ValueError where create refuses"""
     buf = ctypes.create_string_buffer(1 << 17)
     if lib().flbgpu_type_converter_parse_check(*_props(props), buf, len(buf)) != 0:
+        raise ValueError(last_error())
+    return buf.value.decode()
+
+
+class FilterChecklist(_Filter):
+    """filter_checklist: props = [(name, value), ...] in configuration order, e.g. [("file", "/etc/ips.txt"), ("lookup_key", "$remote"),
+    ("mode", "partial"), ("record", "flagged true")] (plugins/filter_checklist/checklist.c); the list is read when the filter is created"""
+
+    def __init__(self, props):
+        self.h = lib().flbgpu_filter_checklist_create(*_props(props))
+        if not self.h:
+            raise ValueError("flbgpu_filter_checklist_create: " + last_error())
+
+    def counters(self):
+        """(records matched, matched records rolled back, lookups that found a non-STR value, size/emit mismatches) since the filter
+        was created (flb_gpu.h flbgpu_checklist_counters)"""
+        o = (c_uint64 * 4)()
+        lib().flbgpu_checklist_counters(self.h, o)
+        return tuple(int(x) for x in o)
+
+
+def checklist_parse_check(props):
+    """the configuration and the loaded list as one line of text (host only); raises ValueError where create refuses"""
+    buf = ctypes.create_string_buffer(1 << 17)
+    if lib().flbgpu_checklist_parse_check(*_props(props), buf, len(buf)) != 0:
         raise ValueError(last_error())
     return buf.value.decode()
 

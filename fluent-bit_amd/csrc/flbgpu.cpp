@@ -2383,6 +2383,7 @@ static int run_any_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_
     else if (f->kind == F_TYPECONV) ok = run_typeconv_dev(f, in, out, st, &ret, garbage);
     else if (f->kind == F_RTAG) ok = run_rtag_dev(f, in, out, st, &ret, garbage);
     else if (f->kind == F_MLFILTER) ok = run_mlfilter_dev(f, in, out, st, &ret, garbage);
+    else if (f->kind == F_CHECKLIST) ok = run_checklist_dev(f, in, out, st, &ret, garbage);
     else ok = f->kind == F_PARSER ? run_parser_dev(f, in, out, st, &ret) : run_grep_dev(f, in, out, st, &ret, garbage);
     if (!ok) return FLBGPU_FILTER_NOTOUCH;      // errors degrade to NOTOUCH (SURVEY 8b "Errors")
     return ret;

@@ -152,7 +152,7 @@ uint64_t l2m_limbs_bits(const uint64_t *limbs, uint64_t n_nan, uint64_t n_pinf, 
 struct KernelProf { const char *name; double ms = 0; uint64_t launches = 0; };
 struct ProfPending { const char *name; hipEvent_t e0, e1; };
 
-enum { F_PARSER = 1, F_GREP = 2, F_L2M = 3, F_JSONFMT = 4, F_MODIFY = 5, F_RECMOD = 6, F_NEST = 7, F_TYPECONV = 8, F_RTAG = 9, F_MLFILTER = 10 };
+enum { F_PARSER = 1, F_GREP = 2, F_L2M = 3, F_JSONFMT = 4, F_MODIFY = 5, F_RECMOD = 6, F_NEST = 7, F_TYPECONV = 8, F_RTAG = 9, F_MLFILTER = 10, F_CHECKLIST = 11 };
 
 struct ModState;                 // filter_modify's program and buffers (modify.cpp)
 void mod_state_destroy(ModState *);
@@ -166,6 +166,8 @@ struct RtagState;                // filter_rewrite_tag's program, buffers and la
 void rtag_state_destroy(RtagState *);
 struct MlFilterState;            // filter_multiline's parser, stream state and buffers (mlfilter.cpp)
 void mlfilter_state_destroy(MlFilterState *);
+struct ChecklistState;           // filter_checklist's list, tables and buffers (checklist.cpp)
+void checklist_state_destroy(ChecklistState *);
 
 struct flbgpu_filter {
     int kind = 0;
@@ -245,6 +247,8 @@ struct flbgpu_filter {
     const uint8_t *rtag_host_base = nullptr;
     // filter_multiline (mode parser, buffer off)
     MlFilterState *mlfilter = nullptr;
+    // filter_checklist
+    ChecklistState *checklist = nullptr;
     bool host_list = false;                     // filter_parser: a list of several parsers with host parsers in it (flbgpu.cpp host_list_rx)
     flbgpu::DevBuf d_hres[flbgpu::MAX_HOST_PARSERS];   // their answers for the chunk at hand
     // msgpack -> JSON output formatter (packfmt.cpp)
@@ -271,6 +275,7 @@ struct flbgpu_filter {
         typeconv_state_destroy(typeconv);
         rtag_state_destroy(rtag);
         mlfilter_state_destroy(mlfilter);
+        checklist_state_destroy(checklist);
         for (auto *b : rule_blobs) delete b;
         for (auto *b : host_rx) if (b) rx::bt_free(b);
         delete l2m_gate;
@@ -331,6 +336,9 @@ bool run_rtag_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk
 
 // filter_multiline entry (mlfilter.cpp); *ret may be -1: a record with a non-empty metadata map, the call is handed back
 bool run_mlfilter_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
+
+// filter_checklist entry (checklist.cpp)
+bool run_checklist_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
 
 // filter_log_to_metrics entry used by flbgpu_filter_run / flbgpu_filter_run_dev
 bool run_l2m_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, hipStream_t st, int *ret);

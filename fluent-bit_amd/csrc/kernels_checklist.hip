@@ -1,11 +1,11 @@
-// kernels_typeconv.hip -- filter_type_converter, a lane per record (typeconv_kernels.inc; shares kdev.inc with the other kernel units)
+// kernels_checklist.hip -- filter_checklist, a lane per record (checklist_kernels.inc; shares kdev.inc with the other kernel units)
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
 #include <type_traits>
 #include "dev.hpp"
 #include "numconv.hpp"
-#include "typeconv.hpp"
+#include "checklist.hpp"
 
 namespace flbgpu {
 
@@ -13,6 +13,6 @@ namespace flbgpu {
 #include "canon_walk.inc"
 #include "ra_lds.inc"
 #include "tc_sink.inc"
-#include "typeconv_kernels.inc"
+#include "checklist_kernels.inc"
 
 }  // namespace flbgpu

@@ -5,55 +5,13 @@
 // original entries go out as rm_walk / mp_canon re-pack them (runs of already-canonical entries as one span); behind them, for every
 // rule whose key the ORIGINAL body holds, to_key and the converted value -- or the value as it was when the conversion fails.
 // Nested values are never interpreted, only walked; the numbers come from numconv.hpp and write straight into the sink.
-// Included inside namespace flbgpu after kdev.inc, canon_walk.inc (rm_walk, RM_MAP_HDR) and ra_lds.inc (the key lookup).
+// Included inside namespace flbgpu after kdev.inc, canon_walk.inc (rm_walk, RM_MAP_HDR), ra_lds.inc (the key lookup) and tc_sink.inc
+// (TcSink and the body header's room).
 
 struct TcTable {
     const LDS_AS uint32_t *w;       // the table's words in LDS
     int nrules;
 };
-
-// the emit pass's sink: [p, limit) is the row's room.  Nothing is stored at or past limit; p keeps counting, so the caller sees
-// both facts -- how long the record would have been and whether a store was withheld.
-struct TcSink {
-    uint8_t *p, *limit;
-    bool over = false;
-    DEV TcSink(uint8_t *dst, uint8_t *lim) : p(dst), limit(lim) {}
-    DEV void note_exact() {}
-    DEV void put(uint32_t b) {
-        if (p < limit) *p = (uint8_t) b; else over = true;
-        p++;
-    }
-    DEV void put32(uint32_t v) { for (int i = 0; i < 4; i++) put((v >> (8 * i)) & 0xffu); }
-    DEV void copy(const uint8_t *src, uint32_t len) {
-        const uint64_t room = p < limit ? (uint64_t) (limit - p) : 0;
-        const uint32_t n = room < len ? (uint32_t) room : len;
-        ByteSink bs(p);
-        bs.copy(src, n);
-        if (n < len) over = true;
-        p += len;
-    }
-};
-
-// a span of the record of any length
-DEV void tc_span(CountSink &s, const uint8_t *, uint64_t len) { s.n += len; }
-DEV void tc_span(TcSink &s, const uint8_t *src, uint64_t len) {
-    while (len > 0x40000000ull) { s.copy(src, 0x40000000u); src += 0x40000000ull; len -= 0x40000000ull; }
-    s.copy(src, (uint32_t) len);
-}
-// the body's map32 header: its room is left open when the record begins and filled when the number of entries is known
-DEV uint8_t *tc_open_hdr(CountSink &s) { s.n += RM_MAP_HDR; return nullptr; }
-DEV uint8_t *tc_open_hdr(TcSink &s) { uint8_t *at = s.p; s.p += RM_MAP_HDR; return at; }
-DEV void tc_close_hdr(CountSink &, uint8_t *, uint64_t) {}
-DEV void tc_close_hdr(TcSink &s, uint8_t *at, uint64_t n) {
-    TcSink hs(at, s.limit);
-    hs.put(0xdf);
-    pk_be(hs, n, 4);
-    if (hs.over) s.over = true;
-}
-
-template <class S> DEV void tc_put_lds(S &s, const LDS_AS uint32_t *e, uint32_t L) {
-    for (uint32_t j = 0; j < L; j++) s.put((e[j >> 2] >> (8 * (j & 3))) & 0xffu);
-}
 
 // flb_ra_get_kv_pair (src/flb_record_accessor.c:788-801, src/flb_ra_key.c:151-236, 374-434) on the original body (ra_lds.inc).  A
 // path that ends on an array index has no key object, and the filter reads that as "not found" (type_converter.c:277-281).

@@ -246,6 +246,48 @@ int flbgpu_type_converter_parse_check(int nprops, const char *const *names, cons
  * length (always 0; the emit pass never stores outside a row's room, and a call that counts one answers NOTOUCH) */
 void flbgpu_type_converter_counters(flbgpu_filter *f, uint64_t out[4]);
 
+/* ---- filter_checklist: replaces cb_checklist_init / cb_checklist_filter / cb_exit ----
+ * plugins/filter_checklist/checklist.c:130-196 (load_file_patterns), 198-267 (init_config, behind the config map of :601-640),
+ * 291-409 (set_record), 411-582 (one call); src/flb_record_accessor.c:803-814 and src/flb_ra_key.c:108-271 (lookup_key).
+ * (names[i], values[i]) are the instance's properties in configuration order, names without case:
+ *   file           the list; the library reads it on the host when the filter is created, as fgets(buf, 2047) reads it: one '\n' and a
+ *                  '\r' in front of it are stripped, empty lines and lines that begin with '#' are skipped, a piece without a newline
+ *                  that is not at the end of the file stops the load (any line of 2046 bytes or more; also a line with a NUL byte in
+ *                  it that is not the last one), and the filter runs with the entries read so far.  No file and a file that cannot be
+ *                  opened give an empty list: cb_checklist_init ignores what init_config answers.
+ *   lookup_key     default "log"; a plain name, `$name`, `$name['a']['b']`, `$name['a'][1]` (a path may end on an index).
+ *   mode           "partial" without case, anything else is exact.
+ *   ignore_case    a bool: A-Z of the list and of the value fold to a-z (tolower in the C locale).
+ *   print_query_time   a bool, accepted (it only logs).
+ *   record         "KEY VALUE", repeatable, split as flb_slist_split_tokens(.., 2) splits: the key is the first entry, the value the
+ *                  LAST one ("record k my val" adds k = "val").  A value "true", "false" or "null" without case goes out as a bool or nil.
+ * Refused, NULL + last_error: an unknown property, a `record` with one entry, a bool that is none, any property but `record` set
+ * more than once -- and, although the reference starts:
+ * more than 64 `record` entries, a record / accessor table of more than 32768 bytes (it sits in LDS), a lookup_key the record
+ * accessor refuses (the reference goes on with a NULL accessor) or that holds `${`, a key name of 128 bytes or more, a list with a
+ * NUL byte at the start of a line (the reference reads buf[-1] there), a list over 4 GB.
+ * One call: only a STR value is looked up.  mode exact: byte equality with an entry, a value of length 0 is never found.  mode partial:
+ * `value LIKE (entry || '%')` as SQLite decides it with case_sensitive_like on -- '%' any run, '_' one character, characters as
+ * SQLite's UTF-8 reader makes them, the value ends at its first NUL, no escape.  No match in the chunk: NOTOUCH.  Otherwise MODIFIED:
+ * the records in front of the first match as one raw span from byte 0, every later unmatched record as the bytes between the
+ * decoder's offsets (group markers in front of it travel with it, those in front of a matched record are lost), a matched record
+ * as 92 92 d7 00 <sec> <nsec>, the metadata re-packed, a map32 header, the body's entries whose key is a STR that no `record` key
+ * equals, re-packed, then every `record` pair in configuration order.  A matched record whose time the encoder refuses is rolled
+ * back and counted as a match; when it is the first record of the chunk the output stays empty until the next match, which then
+ * emits everything in front of it.  Bytes behind a decoder error are dropped.  Runs through flbgpu_filter_run[_dev],
+ * flbgpu_filter_chain_run[_dev], flbgpu_filter_last_counts (records decoded / records emitted) and flbgpu_filter_destroy.
+ * FLBGPU_CHECKLIST_DENSE=1 (a test switch, read at create): the exact table is the smallest power of two above the entry count. */
+flbgpu_filter *flbgpu_filter_checklist_create(int nprops, const char *const *names, const char *const *values);
+/* host only, no device: the configuration and the loaded list as one line of text --
+ * "mode=<exact|partial>;fold=<0|1>;key=K<hex name>{.<hex sub-key>|[<index>]}...|-;records=K<hex key>:<s<hex value>|t|f|n>,...;
+ * entries=<n>;slots=<slots of the exact table, 0 in mode partial>;load=<ok|no file|cannot open|stopped at line n>;digest=<16 hex digits>" (the digest: FNV-1a, 64 bits, over every
+ * entry in order as four bytes of length, little endian, and its bytes) -- 0, or -1 + last_error where create refuses */
+int flbgpu_checklist_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap);
+/* since the filter was created: out[0] records matched, out[1] matched records rolled back, out[2] lookups that found a value that
+ * is no STR, out[3] rows whose emitted length differed from their sized length (always 0; the emit pass never stores outside a
+ * row's room, and a call that counts one answers NOTOUCH) */
+void flbgpu_checklist_counters(flbgpu_filter *f, uint64_t out[4]);
+
 /* ---- filter_rewrite_tag: replaces cb_rewrite_tag_init / cb_rewrite_tag_filter / cb_rewrite_tag_exit ----
  * plugins/filter_rewrite_tag/rewrite_tag.c:112-190 (process_config, behind the config map of :590-613), 356-423 (process_record),
  * 425-557 (one call); src/flb_record_accessor.c:74-230 (the parts of an accessor), 456-619 (ra_translate_*), 644-699
