@@ -341,14 +341,34 @@ def _props(props):
     return n, names, vals
 
 
-class FilterModify(_Filter):
-    """filter_modify: props = [(name, value), ...] in configuration order, e.g. [("Condition", "Key_exists agent"),
-    ("Rename", "host client")] (plugins/filter_modify/modify.c:141-519)"""
+class _PropsFilter(_Filter):
+    """a filter created from a property list: _CREATE names its create function in the C ABI, _COUNTERS the function that reads its
+    four counters (where it has them)"""
+    _CREATE = None
+    _COUNTERS = None
 
     def __init__(self, props):
-        self.h = lib().flbgpu_filter_modify_create(*_props(props))
+        self.h = getattr(lib(), self._CREATE)(*_props(props))
         if not self.h:
-            raise ValueError("flbgpu_filter_modify_create: " + last_error())
+            raise ValueError(self._CREATE + ": " + last_error())
+
+    def _counters(self):
+        o = (c_uint64 * 4)()
+        getattr(lib(), self._COUNTERS)(self.h, o)
+        return tuple(int(x) for x in o)
+
+
+def _parse_check(symbol, props, cap):
+    buf = ctypes.create_string_buffer(cap)
+    if getattr(lib(), symbol)(*_props(props), buf, len(buf)) != 0:
+        raise ValueError(last_error())
+    return buf.value.decode()
+
+
+class FilterModify(_PropsFilter):
+    """filter_modify: props = [(name, value), ...] in configuration order, e.g. [("Condition", "Key_exists agent"),
+    ("Rename", "host client")] (plugins/filter_modify/modify.c:141-519)"""
+    _CREATE = "flbgpu_filter_modify_create"
 
     def overread(self):
         """records whose prefix test would have read past the record in the reference (flb_gpu.h flbgpu_modify_overread)"""
@@ -357,104 +377,70 @@ class FilterModify(_Filter):
 
 def modify_parse_check(props):
     """the program setup() builds from props as one line of text (host only); raises ValueError where create refuses"""
-    buf = ctypes.create_string_buffer(1 << 16)
-    if lib().flbgpu_modify_parse_check(*_props(props), buf, len(buf)) != 0:
-        raise ValueError(last_error())
-    return buf.value.decode()
+    return _parse_check("flbgpu_modify_parse_check", props, 1 << 16)
 
 
-class FilterRecordModifier(_Filter):
+class FilterRecordModifier(_PropsFilter):
     """filter_record_modifier: props = [(name, value), ...] in configuration order, e.g. [("Record", "hostname h"),
     ("Remove_key", "agent")] (plugins/filter_record_modifier/filter_modifier.c:69-155).  filter() may answer -1: a body map of more
     than 65535 entries (:369-377)"""
-
-    def __init__(self, props):
-        self.h = lib().flbgpu_filter_record_modifier_create(*_props(props))
-        if not self.h:
-            raise ValueError("flbgpu_filter_record_modifier_create: " + last_error())
+    _CREATE = "flbgpu_filter_record_modifier_create"
 
 
 def record_modifier_parse_check(props):
     """the program configure() builds from props as one line of text (host only); raises ValueError where create refuses"""
-    buf = ctypes.create_string_buffer(1 << 17)
-    if lib().flbgpu_record_modifier_parse_check(*_props(props), buf, len(buf)) != 0:
-        raise ValueError(last_error())
-    return buf.value.decode()
+    return _parse_check("flbgpu_record_modifier_parse_check", props, 1 << 17)
 
 
-class FilterNest(_Filter):
+class FilterNest(_PropsFilter):
     """filter_nest: props = [(name, value), ...] in configuration order, e.g. [("Operation", "lift"), ("Nested_under", "kubernetes"),
     ("Add_prefix", "k8s_")] (plugins/filter_nest/nest.c:57-175)"""
-
-    def __init__(self, props):
-        self.h = lib().flbgpu_filter_nest_create(*_props(props))
-        if not self.h:
-            raise ValueError("flbgpu_filter_nest_create: " + last_error())
+    _CREATE = "flbgpu_filter_nest_create"
+    _COUNTERS = "flbgpu_nest_counters"
 
     def counters(self):
         """(records built again, compares past the record's end, undefined records, rows over 4 GB) since the filter was created
         (flb_gpu.h flbgpu_nest_counters)"""
-        o = (c_uint64 * 4)()
-        lib().flbgpu_nest_counters(self.h, o)
-        return tuple(int(x) for x in o)
+        return self._counters()
 
 
 def nest_parse_check(props):
     """the program configure() builds from props as one line of text (host only); raises ValueError where create refuses"""
-    buf = ctypes.create_string_buffer(1 << 17)
-    if lib().flbgpu_nest_parse_check(*_props(props), buf, len(buf)) != 0:
-        raise ValueError(last_error())
-    return buf.value.decode()
+    return _parse_check("flbgpu_nest_parse_check", props, 1 << 17)
 
 
-class FilterTypeConverter(_Filter):
+class FilterTypeConverter(_PropsFilter):
     """filter_type_converter: props = [(name, value), ...] in configuration order, e.g. [("str_key", "status status_i int"),
     ("int_key", "size size_s string")] (plugins/filter_type_converter/type_converter.c:57-140)"""
-
-    def __init__(self, props):
-        self.h = lib().flbgpu_filter_type_converter_create(*_props(props))
-        if not self.h:
-            raise ValueError("flbgpu_filter_type_converter_create: " + last_error())
+    _CREATE = "flbgpu_filter_type_converter_create"
+    _COUNTERS = "flbgpu_type_converter_counters"
 
     def counters(self):
         """(conversions done, conversions failed, conversions C leaves undefined, size/emit mismatches) since the filter was created
         (flb_gpu.h flbgpu_type_converter_counters)"""
-        o = (c_uint64 * 4)()
-        lib().flbgpu_type_converter_counters(self.h, o)
-        return tuple(int(x) for x in o)
+        return self._counters()
 
 
 def type_converter_parse_check(props):
     """the rules configure() keeps from props, in its order, as one line of text (host only); raises ValueError where create refuses"""
-    buf = ctypes.create_string_buffer(1 << 17)
-    if lib().flbgpu_type_converter_parse_check(*_props(props), buf, len(buf)) != 0:
-        raise ValueError(last_error())
-    return buf.value.decode()
+    return _parse_check("flbgpu_type_converter_parse_check", props, 1 << 17)
 
 
-class FilterChecklist(_Filter):
+class FilterChecklist(_PropsFilter):
     """filter_checklist: props = [(name, value), ...] in configuration order, e.g. [("file", "/etc/ips.txt"), ("lookup_key", "$remote"),
     ("mode", "partial"), ("record", "flagged true")] (plugins/filter_checklist/checklist.c); the list is read when the filter is created"""
-
-    def __init__(self, props):
-        self.h = lib().flbgpu_filter_checklist_create(*_props(props))
-        if not self.h:
-            raise ValueError("flbgpu_filter_checklist_create: " + last_error())
+    _CREATE = "flbgpu_filter_checklist_create"
+    _COUNTERS = "flbgpu_checklist_counters"
 
     def counters(self):
         """(records matched, matched records rolled back, lookups that found a non-STR value, size/emit mismatches) since the filter
         was created (flb_gpu.h flbgpu_checklist_counters)"""
-        o = (c_uint64 * 4)()
-        lib().flbgpu_checklist_counters(self.h, o)
-        return tuple(int(x) for x in o)
+        return self._counters()
 
 
 def checklist_parse_check(props):
     """the configuration and the loaded list as one line of text (host only); raises ValueError where create refuses"""
-    buf = ctypes.create_string_buffer(1 << 17)
-    if lib().flbgpu_checklist_parse_check(*_props(props), buf, len(buf)) != 0:
-        raise ValueError(last_error())
-    return buf.value.decode()
+    return _parse_check("flbgpu_checklist_parse_check", props, 1 << 17)
 
 
 class RtagEmittedRec(ctypes.Structure):
@@ -469,15 +455,16 @@ class RtagEmitted(ctypes.Structure):
 RTAG_EMIT_CB = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t)
 
 
-class FilterRewriteTag(_Filter):
+class FilterRewriteTag(_PropsFilter):
     """filter_rewrite_tag: props = [(name, value), ...] in configuration order, e.g. [("Rule", "$log ^.*error.*$ err.$TAG false")]
     (plugins/filter_rewrite_tag/rewrite_tag.c:112-190).  tag: the tag of the following calls; emitter: a function
     (tag bytes, record bytes) -> int that stands where in_emitter_add_record stands -- an answer < 0 keeps the record"""
 
+    _CREATE = "flbgpu_filter_rewrite_tag_create"
+    _COUNTERS = "flbgpu_rewrite_tag_counters"
+
     def __init__(self, props, tag=b"", emitter=None):
-        self.h = lib().flbgpu_filter_rewrite_tag_create(*_props(props))
-        if not self.h:
-            raise ValueError("flbgpu_filter_rewrite_tag_create: " + last_error())
+        super().__init__(props)
         self._cb = None
         self.set_tag(tag)
         if emitter is not None:
@@ -518,17 +505,12 @@ class FilterRewriteTag(_Filter):
     def counters(self):
         """(records emitted, emissions refused, size/emit mismatches, tag bytes written) since the filter was created
         (flb_gpu.h flbgpu_rewrite_tag_counters)"""
-        o = (c_uint64 * 4)()
-        lib().flbgpu_rewrite_tag_counters(self.h, o)
-        return tuple(int(x) for x in o)
+        return self._counters()
 
 
 def rewrite_tag_parse_check(props):
     """the rules process_config builds from props as one line of text (host only); raises ValueError where create refuses"""
-    buf = ctypes.create_string_buffer(1 << 17)
-    if lib().flbgpu_rewrite_tag_parse_check(*_props(props), buf, len(buf)) != 0:
-        raise ValueError(last_error())
-    return buf.value.decode()
+    return _parse_check("flbgpu_rewrite_tag_parse_check", props, 1 << 17)
 
 
 JSON_FORMAT = {"json": 1, "stream": 2, "lines": 3}                                        # flb_pack_to_json_format_type

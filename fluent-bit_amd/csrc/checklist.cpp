@@ -2,7 +2,7 @@
 // init_config (:198-267) read it, the list loader (load_file_patterns :130-196) restated over the file's bytes, the lookup
 // structures for HBM (an open-addressed table for mode exact, first-byte buckets for mode partial), and one cb_checklist_filter
 // call on a device chunk (:411-582).  The per-record work is checklist_kernels.inc.
-#include "host_int.hpp"
+#include "filter_host.hpp"
 #include "checklist.hpp"
 
 using namespace flbgpu;
@@ -21,13 +21,6 @@ struct CProgram {
     int load = LOAD_OK, stop_line = 0;
     std::vector<std::string> entries;    // in file order, as they were added (folded when ignore_case is set)
 };
-
-std::string hexs(const std::string &s) {
-    static const char *hx = "0123456789abcdef";
-    std::string o;
-    for (unsigned char c : s) { o.push_back(hx[c >> 4]); o.push_back(hx[c & 15]); }
-    return o;
-}
 
 // flb_utils_bool (src/flb_utils.c:757-771)
 int bool_of(const std::string &v) {
@@ -243,9 +236,7 @@ std::string describe(const CProgram &pg) {
 }
 
 bool checked_program(int nprops, const char *const *names, const char *const *values, CProgram &pg, std::vector<uint32_t> &table) {
-    std::string why;
-    if (nprops < 0 || (nprops > 0 && (!names || !values))) { set_err("filter_checklist: bad arguments"); return false; }
-    if (!parse_program(nprops, names, values, pg, why)) { set_err("filter_checklist: %s", why.c_str()); return false; }
+    if (!parse_front("checklist", nprops, names, values, [&](std::string &why) { return parse_program(nprops, names, values, pg, why); })) return false;
     build_table(pg, table);
     if (table.size() * 4 > CL_MAX_TABLE_BYTES) { set_err("filter_checklist: record / accessor table larger than %u bytes", CL_MAX_TABLE_BYTES); return false; }
     uint64_t arena = 0;
@@ -254,36 +245,24 @@ bool checked_program(int nprops, const char *const *names, const char *const *va
     return true;
 }
 
-}  // namespace
-
-struct ChecklistState {
+struct ChecklistState : FilterState {
+    struct Words { unsigned long long firsts[5], counts[7]; };
     int mode = 0, fold = 0;
     uint32_t table_bytes = 0, arena_bytes = 0, nslots = 0, nents = 0;
     uint64_t matched = 0, rolled = 0, nonstr = 0, mismatch = 0;        // since the filter was created (flbgpu_checklist_counters)
-    DevBuf d_table, d_arena, d_slots, d_bucket, d_ents, d_words, d_flags, d_enc;
-    PinnedBuf hp_words;
+    ScopedDevBuf d_table, d_arena, d_slots, d_bucket, d_ents, d_flags, d_enc;
+    CallWords<Words> words;
+    bool run(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) override;
 };
 
-void checklist_state_destroy(ChecklistState *m) {
-    if (!m) return;
-    DevBuf *all[] = {&m->d_table, &m->d_arena, &m->d_slots, &m->d_bucket, &m->d_ents, &m->d_words, &m->d_flags, &m->d_enc};
-    for (DevBuf *b : all) b->release();
-    m->hp_words.release();
-    delete m;
-}
+}  // namespace
 
 extern "C" int flbgpu_checklist_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap) {
     CProgram pg;
     std::vector<uint32_t> table;
     if (!checked_program(nprops, names, values, pg, table)) return -1;
-    const std::string d = describe(pg);
-    if (desc && cap) { const size_t n = d.size() < cap - 1 ? d.size() : cap - 1; memcpy(desc, d.data(), n); desc[n] = 0; }
+    put_desc(desc, cap, describe(pg));
     return 0;
-}
-
-static bool upload(DevBuf &b, const void *src, size_t bytes) {
-    if (!b.ensure(bytes + 16)) return false;
-    return bytes == 0 || hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
 }
 
 extern "C" flbgpu_filter *flbgpu_filter_checklist_create(int nprops, const char *const *names, const char *const *values) {
@@ -330,15 +309,14 @@ extern "C" flbgpu_filter *flbgpu_filter_checklist_create(int nprops, const char 
     auto *f = new flbgpu_filter();
     f->kind = F_CHECKLIST;
     auto *m = new ChecklistState();
-    f->checklist = m;
+    f->state = m;
     m->mode = pg.mode; m->fold = pg.fold;
     m->table_bytes = (uint32_t) (table.size() * 4);
     m->arena_bytes = (uint32_t) arena.size();
     m->nslots = nslots;
     m->nents = (uint32_t) (ents.size() / 2);
-    if (!filter_common_init(f) || !upload(m->d_table, table.data(), m->table_bytes) || !upload(m->d_arena, arena.data(), arena.size()) ||
-        !upload(m->d_slots, slots.data(), slots.size() * 4) || !upload(m->d_bucket, bucket.data(), bucket.size() * 4) ||
-        !upload(m->d_ents, ents.data(), ents.size() * 4)) {
+    if (!filter_common_init(f) || !upload(m->d_table, table) || !upload(m->d_arena, arena.data(), arena.size()) ||
+        !upload(m->d_slots, slots) || !upload(m->d_bucket, bucket) || !upload(m->d_ents, ents)) {
         set_err("filter_checklist: the list could not be placed on the device");
         delete f;
         return nullptr;
@@ -348,44 +326,33 @@ extern "C" flbgpu_filter *flbgpu_filter_checklist_create(int nprops, const char 
 
 extern "C" void flbgpu_checklist_counters(flbgpu_filter *f, uint64_t out[4]) {
     out[0] = out[1] = out[2] = out[3] = 0;
-    if (!f || f->kind != F_CHECKLIST || !f->checklist) return;
-    out[0] = f->checklist->matched; out[1] = f->checklist->rolled; out[2] = f->checklist->nonstr; out[3] = f->checklist->mismatch;
+    if (auto *m = state_of<ChecklistState>(f, F_CHECKLIST)) { out[0] = m->matched; out[1] = m->rolled; out[2] = m->nonstr; out[3] = m->mismatch; }
 }
 
 // cb_checklist_filter (:411-582) on a device chunk.  The loop ends at the first record the decoder refuses; what stands behind it,
 // and undecodable bytes behind the rows, are dropped from a MODIFIED answer and change nothing else.
-bool run_checklist_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool) {
-    ChecklistState *m = f->checklist;
+bool ChecklistState::run(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool) {
     uint64_t n = in->n;
     *ret = FLBGPU_FILTER_NOTOUCH;
     f->last_in = 0; f->last_out = 0;
     if (n == 0) return true;
-    struct Words { unsigned long long firsts[5], counts[7]; };
-    if (!m->d_words.ensure(sizeof(Words)) || !m->hp_words.ensure(sizeof(Words) + sizeof(uint64_t))) return false;
-    if (!f->d_len.ensure(n * sizeof(uint32_t)) || !m->d_enc.ensure(n * sizeof(uint32_t)) || !m->d_flags.ensure(n) ||
-        !f->d_off.ensure((n + 1) * sizeof(uint64_t)) || !f->d_scan_tmp.ensure(scan_tmp_elems(n) * sizeof(uint64_t)))
-        return false;
-    Words *dw = m->d_words.as<Words>();
-    Words &hw = *m->hp_words.as<Words>();
-    uint64_t &total = *(uint64_t *) (m->hp_words.as<uint8_t>() + sizeof(Words));
+    if (!words.ensure() || !ensure_row_columns(f, n) || !d_enc.ensure(n * sizeof(uint32_t)) || !d_flags.ensure(n)) return false;
+    Words *dw = words.dev();
+    Words &hw = words.host();
+    uint64_t &total = words.total();
     ChecklistArgs a;
     memset(&a, 0, sizeof(a));
     a.data = (const uint8_t *) in->data; a.row_off = in->row_off; a.n = n;
-    a.table = m->d_table.as<uint32_t>(); a.table_bytes = m->table_bytes;
-    a.mode = m->mode; a.fold = m->fold;
-    a.arena = m->d_arena.as<uint8_t>(); a.arena_bytes = m->arena_bytes;
-    a.slots = m->d_slots.as<uint32_t>(); a.nslots = m->nslots;
-    a.bucket_off = m->d_bucket.as<uint32_t>(); a.ents = m->d_ents.as<uint32_t>(); a.nents = m->nents;
-    a.flags = m->d_flags.as<uint8_t>(); a.enc_len = m->d_enc.as<uint32_t>(); a.len = f->d_len.as<uint32_t>();
+    a.table = d_table.as<uint32_t>(); a.table_bytes = table_bytes;
+    a.mode = mode; a.fold = fold;
+    a.arena = d_arena.as<uint8_t>(); a.arena_bytes = arena_bytes;
+    a.slots = d_slots.as<uint32_t>(); a.nslots = nslots;
+    a.bucket_off = d_bucket.as<uint32_t>(); a.ents = d_ents.as<uint32_t>(); a.nents = nents;
+    a.flags = d_flags.as<uint8_t>(); a.enc_len = d_enc.as<uint32_t>(); a.len = f->d_len.as<uint32_t>();
     a.firsts = dw->firsts; a.counts = dw->counts;
     auto size_pass = [&](const char *name) {
-        memset(&hw, 0xff, sizeof(hw.firsts));
-        memset(hw.counts, 0, sizeof(hw.counts));
-        HIPOK(hipMemcpyAsync(dw, &hw, sizeof(hw), hipMemcpyHostToDevice, st));
-        { ProfScope ps(f, st, name); launch_checklist(a, false, st); }
-        HIPOK(hipMemcpyAsync(&hw, dw, sizeof(hw), hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
-        return true;
+        return words.pass(f, st, name, [](Words &w) { memset(w.firsts, 0xff, sizeof(w.firsts)); memset(w.counts, 0, sizeof(w.counts)); },
+                          [&] { launch_checklist(a, false, st); });
     };
     if (!size_pass("k_checklist(size)")) return false;
     const unsigned long long fb = hw.firsts[0];
@@ -395,7 +362,7 @@ bool run_checklist_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_
         a.n = n = fb;
         if (!size_pass("k_checklist(size, in front of a decoder error)")) return false;
     }
-    m->matched += hw.counts[2]; m->rolled += hw.counts[3]; m->nonstr += hw.counts[4];
+    matched += hw.counts[2]; rolled += hw.counts[3]; nonstr += hw.counts[4];
     f->last_in = hw.counts[0];
     f->last_out = hw.counts[0];
     if (hw.counts[5]) { set_err("filter_checklist: a record's output is larger than 4 GB"); return false; }
@@ -413,19 +380,18 @@ bool run_checklist_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_
     }
     a.first_eff = eff;
     { ProfScope ps(f, st, "k_checklist_plan"); launch_checklist_plan(a, st); }
-    { ProfScope ps(f, st, "k_scan"); launch_scan(a.len, n, f->d_scan_tmp.as<uint64_t>(), f->d_off.as<uint64_t>(), st, nullptr); }
-    HIPOK(hipMemcpyAsync(&total, f->d_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    // (the records in the encoder come over in the scan's sync)
+    if (!scan_lengths_queue(f, st, a.len, n, &total)) return false;
     HIPOK(hipMemcpyAsync(&hw.counts[1], &dw->counts[1], sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
+    if (!scan_lengths_wait(f, st, &total)) return false;
     if (total == 0) return true;                                         // (a first record that matched, was refused, and nothing else)
-    if (!f->d_out.ensure(total + 16)) return false;
     a.out_off = f->d_off.as<uint64_t>(); a.out = f->d_out.as<uint8_t>();
     { ProfScope ps(f, st, "k_checklist(emit)"); launch_checklist(a, true, st); }
     HIPOK(hipMemcpyAsync(&hw.counts[6], &dw->counts[6], sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
-    m->mismatch += hw.counts[6];
+    mismatch += hw.counts[6];
     if (hw.counts[6]) { set_err("filter_checklist: %llu rows were emitted with another length than they were sized", hw.counts[6]); return false; }
-    out->data = f->d_out.p; out->row_off = f->d_off.as<uint64_t>(); out->n = n; out->bytes = total;
+    set_out(f, out, n, total);
     f->last_out = hw.counts[1];
     *ret = FLBGPU_FILTER_MODIFIED;
     return true;

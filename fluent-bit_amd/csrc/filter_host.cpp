@@ -1,0 +1,47 @@
+// filter_host.cpp -- the host skeleton of the lane-per-record filters (filter_host.hpp)
+#include "filter_host.hpp"
+
+namespace flbgpu {
+
+std::string hexs(const std::string &s) {
+    static const char *hx = "0123456789abcdef";
+    std::string o;
+    for (unsigned char c : s) { o.push_back(hx[c >> 4]); o.push_back(hx[c & 15]); }
+    return o;
+}
+
+bool bad_args(int nprops, const char *const *names, const char *const *values) { return nprops < 0 || (nprops > 0 && (!names || !values)); }
+
+void put_desc(char *desc, size_t cap, const std::string &text) {
+    if (!desc || !cap) return;
+    const size_t n = text.size() < cap - 1 ? text.size() : cap - 1;
+    memcpy(desc, text.data(), n);
+    desc[n] = 0;
+}
+
+bool upload(DevBuf &b, const void *src, size_t bytes) {
+    if (!b.ensure(bytes + 16)) return false;
+    if (bytes) HIPOK(hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
+    return true;
+}
+
+bool ensure_row_columns(flbgpu_filter *f, uint64_t n) {
+    return f->d_len.ensure(n * sizeof(uint32_t)) && f->d_off.ensure((n + 1) * sizeof(uint64_t)) && f->d_scan_tmp.ensure(scan_tmp_elems(n) * sizeof(uint64_t));
+}
+
+bool scan_lengths_queue(flbgpu_filter *f, hipStream_t st, const uint32_t *len, uint64_t n, uint64_t *total) {
+    { ProfScope ps(f, st, "k_scan"); launch_scan(len, n, f->d_scan_tmp.as<uint64_t>(), f->d_off.as<uint64_t>(), st, nullptr); }
+    HIPOK(hipMemcpyAsync(total, f->d_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    return true;
+}
+
+bool scan_lengths_wait(flbgpu_filter *f, hipStream_t st, const uint64_t *total) {
+    HIPOK(hipStreamSynchronize(st));
+    return f->d_out.ensure(*total + 16);
+}
+
+void set_out(flbgpu_filter *f, flbgpu_dev_chunk *out, uint64_t n, uint64_t total) {
+    out->data = f->d_out.p; out->row_off = f->d_off.as<uint64_t>(); out->n = n; out->bytes = total;
+}
+
+}  // namespace flbgpu

@@ -8,6 +8,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <string>
 #include <strings.h>
 #include <vector>
@@ -45,7 +46,8 @@ struct DevBuf {
     void release() { if (p) (void) hipFree(p); p = nullptr; cap = 0; }
     template <class T> T *as() const { return (T *) p; }
 };
-// a function-local device buffer: released on every return path (DevBuf itself is a plain member type that its owner releases)
+// a device buffer that releases itself: function-local ones on every return path, and the members of a FilterState with their owner
+// (DevBuf itself is a plain member type that its owner releases by hand)
 struct ScopedDevBuf : DevBuf {
     ScopedDevBuf() = default;
     ScopedDevBuf(const ScopedDevBuf &) = delete;
@@ -69,6 +71,12 @@ struct PinnedBuf {
     }
     void release() { if (p) (void) hipHostFree(p); p = nullptr; cap = 0; }
     template <class T> T *as() const { return (T *) p; }
+};
+struct ScopedPinnedBuf : PinnedBuf {
+    ScopedPinnedBuf() = default;
+    ScopedPinnedBuf(const ScopedPinnedBuf &) = delete;
+    ScopedPinnedBuf &operator=(const ScopedPinnedBuf &) = delete;
+    ~ScopedPinnedBuf() { release(); }
 };
 
 // uploads vectors of one table set into a single device allocation
@@ -154,20 +162,13 @@ struct ProfPending { const char *name; hipEvent_t e0, e1; };
 
 enum { F_PARSER = 1, F_GREP = 2, F_L2M = 3, F_JSONFMT = 4, F_MODIFY = 5, F_RECMOD = 6, F_NEST = 7, F_TYPECONV = 8, F_RTAG = 9, F_MLFILTER = 10, F_CHECKLIST = 11 };
 
-struct ModState;                 // filter_modify's program and buffers (modify.cpp)
-void mod_state_destroy(ModState *);
-struct RecmodState;              // filter_record_modifier's program and buffers (recmod.cpp)
-void recmod_state_destroy(RecmodState *);
-struct NestState;                // filter_nest's program and buffers (nest.cpp)
-void nest_state_destroy(NestState *);
-struct TypeconvState;            // filter_type_converter's program and buffers (typeconv.cpp)
-void typeconv_state_destroy(TypeconvState *);
-struct RtagState;                // filter_rewrite_tag's program, buffers and last emissions (rtag.cpp)
-void rtag_state_destroy(RtagState *);
-struct MlFilterState;            // filter_multiline's parser, stream state and buffers (mlfilter.cpp)
-void mlfilter_state_destroy(MlFilterState *);
-struct ChecklistState;           // filter_checklist's list, tables and buffers (checklist.cpp)
-void checklist_state_destroy(ChecklistState *);
+// What a lane-per-record filter (kinds F_MODIFY .. F_CHECKLIST) keeps behind its flbgpu_filter: its program and its buffers, which
+// release themselves (ScopedDevBuf, ScopedPinnedBuf), and one cb_filter call on a device chunk.  garbage: undecodable bytes follow the
+// rows.  false: failure (flbgpu_last_error says which); *ret may be -1 where the filter hands a call back.
+struct FilterState {
+    virtual ~FilterState() {}
+    virtual bool run(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) = 0;
+};
 
 struct flbgpu_filter {
     int kind = 0;
@@ -231,24 +232,13 @@ struct flbgpu_filter {
     // filter_log_to_metrics whose regex / exclude rules hold a pattern that is not a regular expression: the rules live in this hidden
     // filter_grep (host rules, flbgpu.cpp) and run in FRONT of the metric kernels, which then see the kept records and no rules
     flbgpu_filter *l2m_gate = nullptr;
-    // filter_modify
-    ModState *mod = nullptr;
-    // filter_record_modifier
-    RecmodState *recmod = nullptr;
-    // filter_nest
-    NestState *nest = nullptr;
-    // filter_type_converter
-    TypeconvState *typeconv = nullptr;
-    // filter_rewrite_tag; during a host-level call (flbgpu_filter_chain_run): the emitter's callback is asked, and the chunk at
+    // filter_modify, record_modifier, nest, type_converter, rewrite_tag, multiline, checklist: the one that `kind` names (filter_host.hpp)
+    FilterState *state = nullptr;
+    // filter_rewrite_tag during a host-level call (flbgpu_filter_chain_run): the emitter's callback is asked, and the chunk at
     // rtag_dev_base is the caller's buffer at rtag_host_base
-    RtagState *rtag = nullptr;
     bool rtag_host_call = false;
     const void *rtag_dev_base = nullptr;
     const uint8_t *rtag_host_base = nullptr;
-    // filter_multiline (mode parser, buffer off)
-    MlFilterState *mlfilter = nullptr;
-    // filter_checklist
-    ChecklistState *checklist = nullptr;
     bool host_list = false;                     // filter_parser: a list of several parsers with host parsers in it (flbgpu.cpp host_list_rx)
     flbgpu::DevBuf d_hres[flbgpu::MAX_HOST_PARSERS];   // their answers for the chunk at hand
     // msgpack -> JSON output formatter (packfmt.cpp)
@@ -269,13 +259,7 @@ struct flbgpu_filter {
     ~flbgpu_filter() {
         for (auto &p : pending) { (void) hipEventDestroy(p.e0); (void) hipEventDestroy(p.e1); }
         if (l2m) l2m_state_destroy(l2m);
-        mod_state_destroy(mod);
-        recmod_state_destroy(recmod);
-        nest_state_destroy(nest);
-        typeconv_state_destroy(typeconv);
-        rtag_state_destroy(rtag);
-        mlfilter_state_destroy(mlfilter);
-        checklist_state_destroy(checklist);
+        delete state;
         for (auto *b : rule_blobs) delete b;
         for (auto *b : host_rx) if (b) rx::bt_free(b);
         delete l2m_gate;
@@ -320,25 +304,6 @@ bool staged_download(flbgpu_filter *f, void *dst, const void *src, size_t bytes)
 // row_off == NULL ("raw chunk bytes" in HBM): the records are found on the device
 bool resolve_raw_chunk(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *resolved, bool *garbage);
 }
-
-// filter_modify entry used by flbgpu_filter_run / flbgpu_filter_run_dev (modify.cpp); garbage: undecodable bytes follow the rows
-bool run_modify_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
-// filter_record_modifier entry (recmod.cpp); *ret may be -1: a body map over the reference's 65535-entry limit
-bool run_recmod_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
-// filter_nest entry (nest.cpp)
-bool run_nest_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
-
-// filter_type_converter entry (typeconv.cpp)
-bool run_typeconv_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
-
-// filter_rewrite_tag entry (rtag.cpp)
-bool run_rtag_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
-
-// filter_multiline entry (mlfilter.cpp); *ret may be -1: a record with a non-empty metadata map, the call is handed back
-bool run_mlfilter_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
-
-// filter_checklist entry (checklist.cpp)
-bool run_checklist_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage);
 
 // filter_log_to_metrics entry used by flbgpu_filter_run / flbgpu_filter_run_dev
 bool run_l2m_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, hipStream_t st, int *ret);

@@ -4,10 +4,12 @@
 // chunk at once -- the records are the items of the multiline core (ml.cpp, ml_kernels.inc), mlfilter_kernels.inc builds the groups'
 // records.  No CPU path.
 #include "mlfilter.hpp"
+#include "filter_host.hpp"
 
 using namespace flbgpu;
 
-struct MlFilterState {
+namespace {
+struct MlFilterState : FilterState {
     flbgpu_ml_parser *parser = nullptr;
     bool parser_owned = false;
     std::string parser_name, key;
@@ -15,16 +17,12 @@ struct MlFilterState {
     int nrules = 0;
     MlfStream stream;
     MlfTotals tot;
-    DevBuf d_words, d_misc, d_keep, d_koff, d_ls, d_ll, d_irow, d_cls, d_tsec, d_tnsec, d_info, d_F, d_sin, d_act, d_c, d_coff, d_head, d_gidx, d_ghead,
+    ScopedDevBuf d_words, d_misc, d_keep, d_koff, d_ls, d_ll, d_irow, d_cls, d_tsec, d_tnsec, d_info, d_F, d_sin, d_act, d_c, d_coff, d_head, d_gidx, d_ghead,
            d_ovr, d_slow, d_fs_tmp, d_ev, d_evoff, d_regidx, d_plen, d_po, d_pre, d_dup, d_nrec, d_ridx, d_rows, d_carry;
-    ~MlFilterState() {
-        DevBuf *all[] = {&d_words, &d_misc, &d_keep, &d_koff, &d_ls, &d_ll, &d_irow, &d_cls, &d_tsec, &d_tnsec, &d_info, &d_F, &d_sin, &d_act, &d_c, &d_coff, &d_head,
-                         &d_gidx, &d_ghead, &d_ovr, &d_slow, &d_fs_tmp, &d_ev, &d_evoff, &d_regidx, &d_plen, &d_po, &d_pre, &d_dup, &d_nrec, &d_ridx, &d_rows, &d_carry};
-        for (DevBuf *b : all) b->release();
-        if (parser && parser_owned) flbgpu_ml_parser_destroy(parser);
-    }
+    ~MlFilterState() override { if (parser && parser_owned) flbgpu_ml_parser_destroy(parser); }
+    bool run(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) override;
 };
-void mlfilter_state_destroy(MlFilterState *m) { delete m; }
+}  // namespace
 
 namespace flbgpu {
 uint64_t mlf_rows_of_call(uint64_t n, unsigned long long first_bad) { return first_bad == ~0ull || first_bad > n ? n : (uint64_t) first_bad; }
@@ -129,8 +127,8 @@ static flbgpu_ml_parser *resolve_parser(const MlfConfig &c, int nparsers, const 
     return p;
 }
 
-static bool bad_args(int nprops, const char *const *names, const char *const *values) {
-    if (nprops < 0 || (nprops > 0 && (!names || !values))) return true;
+// (this front end reads every name and value as a C string: an entry without one is a bad argument too)
+static bool null_entry(int nprops, const char *const *names, const char *const *values) {
     for (int i = 0; i < nprops; i++) if (!names[i] || !values[i]) return true;
     return false;
 }
@@ -140,7 +138,7 @@ static const char *type_name(int t) { return t == ML_REGEX ? "regex" : t == ML_E
 static bool build(int nprops, const char *const *names, const char *const *values, int nparsers, const char *const *parser_names,
                   flbgpu_ml_parser *const *parsers, MlFilterState *m, MlArgs &ma, std::string &why) {
     MlfConfig c;
-    if (bad_args(nprops, names, values)) { why = "bad arguments"; return false; }
+    if (null_entry(nprops, names, values)) { why = "bad arguments"; return false; }
     if (!parse_config(nprops, names, values, c, why)) return false;
     bool owned = false;
     flbgpu_ml_parser *p = resolve_parser(c, nparsers, parser_names, parsers, &owned, why);
@@ -160,17 +158,15 @@ static bool build(int nprops, const char *const *names, const char *const *value
 
 // host only: the device is not touched.  A name of parser_names counts as defined whether or not a handle comes with it (the
 // definitions live on the device); a built-in is described from its table, never created
-extern "C" int flbgpu_multiline_parse_check(int nprops, const char *const *names, const char *const *values, int nparsers, const char *const *parser_names,
-                                            flbgpu_ml_parser *const *parsers, char *desc, size_t cap) {
+static bool describe(int nprops, const char *const *names, const char *const *values, int nparsers, const char *const *parser_names,
+                     flbgpu_ml_parser *const *parsers, std::string &text, std::string &why) {
     MlfConfig c;
-    std::string why;
-    auto refuse = [&]() { set_err("filter_multiline: %s", why.c_str()); return -1; };
-    if (bad_args(nprops, names, values)) { why = "bad arguments"; return refuse(); }
-    if (!parse_config(nprops, names, values, c, why)) return refuse();
-    if (c.parser == "docker" || c.parser == "cri") { why = "a multiline parser with a parser in front ('" + c.parser + "') is not built"; return refuse(); }
+    if (null_entry(nprops, names, values)) { why = "bad arguments"; return false; }
+    if (!parse_config(nprops, names, values, c, why)) return false;
+    if (c.parser == "docker" || c.parser == "cri") { why = "a multiline parser with a parser in front ('" + c.parser + "') is not built"; return false; }
     int custom = -1;
     for (int i = 0; i < nparsers && custom < 0; i++) if (parser_names && parser_names[i] && c.parser == parser_names[i]) custom = i;
-    if (custom < 0 && !is_builtin(c.parser)) { why = "multiline parser '" + c.parser + "' is not defined"; return refuse(); }
+    if (custom < 0 && !is_builtin(c.parser)) { why = "multiline parser '" + c.parser + "' is not defined"; return false; }
     std::string key = c.has_key ? c.key : custom < 0 ? "log" : "";
     bool has_key = c.has_key || custom < 0;
     std::string extra;
@@ -180,8 +176,8 @@ extern "C" int flbgpu_multiline_parse_check(int nprops, const char *const *names
         bool has_sub = false;
         int nrules = 0;
         memset(&ma, 0, sizeof(ma));
-        if (!ml_parser_args(parsers[custom], ma, pkey, has_sub, nrules)) { why = "multiline parser '" + c.parser + "' is not initialised"; return refuse(); }
-        if (has_sub) { why = "a multiline parser with a parser in front ('" + c.parser + "') is not built"; return refuse(); }
+        if (!ml_parser_args(parsers[custom], ma, pkey, has_sub, nrules)) { why = "multiline parser '" + c.parser + "' is not initialised"; return false; }
+        if (has_sub) { why = "a multiline parser with a parser in front ('" + c.parser + "') is not built"; return false; }
         if (!c.has_key && !pkey.empty()) { key = pkey; has_key = true; }
         char b[128];
         snprintf(b, sizeof(b), " type=%s rules=%d buffer_limit=%llu", type_name(ma.p.type), nrules, (unsigned long long) ma.p.buffer_limit);
@@ -193,7 +189,16 @@ extern "C" int flbgpu_multiline_parse_check(int nprops, const char *const *names
         snprintf(b, sizeof(b), " type=regex rules=%d buffer_limit=%llu", nr, 2ull * 1024 * 1024);
         extra = b;
     }
-    if (desc && cap) snprintf(desc, cap, "parser=%s key_content=%s%s", c.parser.c_str(), has_key ? key.c_str() : "(none)", extra.c_str());
+    text = "parser=" + c.parser + " key_content=" + (has_key ? key : std::string("(none)")) + extra;
+    return true;
+}
+
+extern "C" int flbgpu_multiline_parse_check(int nprops, const char *const *names, const char *const *values, int nparsers, const char *const *parser_names,
+                                            flbgpu_ml_parser *const *parsers, char *desc, size_t cap) {
+    std::string text;
+    if (!parse_front("multiline", nprops, names, values, [&](std::string &why) { return describe(nprops, names, values, nparsers, parser_names, parsers, text, why); }))
+        return -1;
+    put_desc(desc, cap, text);
     return 0;
 }
 
@@ -201,42 +206,44 @@ extern "C" flbgpu_filter *flbgpu_filter_multiline_create(int nprops, const char 
                                                          const char *const *parser_names, flbgpu_ml_parser *const *parsers) {
     auto *m = new MlFilterState();
     MlArgs ma;
-    std::string why;
-    if (!build(nprops, names, values, nparsers, parser_names, parsers, m, ma, why)) { set_err("filter_multiline: %s", why.c_str()); delete m; return nullptr; }
+    if (!parse_front("multiline", nprops, names, values, [&](std::string &why) { return build(nprops, names, values, nparsers, parser_names, parsers, m, ma, why); })) {
+        delete m;
+        return nullptr;
+    }
     auto *f = new flbgpu_filter();
     f->kind = F_MLFILTER;
-    f->mlfilter = m;
+    f->state = m;
     if (!filter_common_init(f) || !m->d_carry.ensure(64)) { delete f; return nullptr; }
     return f;
 }
 
 extern "C" void flbgpu_multiline_counters(flbgpu_filter *f, uint64_t out[4]) {
     out[0] = out[1] = out[2] = out[3] = 0;
-    if (!f || f->kind != F_MLFILTER || !f->mlfilter) return;
-    const MlfTotals &t = f->mlfilter->tot;
+    auto *m = state_of<MlFilterState>(f, F_MLFILTER);
+    if (!m) return;
+    const MlfTotals &t = m->tot;
     out[0] = t.ok_records; out[1] = t.truncations; out[2] = t.handed_back; out[3] = t.mismatch;
 }
 
 extern "C" int flbgpu_multiline_state(flbgpu_filter *f) {
-    if (!f || f->kind != F_MLFILTER || !f->mlfilter) return -1;
-    return (int) f->mlfilter->stream.state - 1;
+    auto *m = state_of<MlFilterState>(f, F_MLFILTER);
+    return m ? (int) m->stream.state - 1 : -1;
 }
 
 // cb_ml_filter (:839-909) on a device chunk.  Launch order: class -> scan(rows handed out) -> items -> match -> fix -> [function scan ->
 // act -> scans -> group heads -> first truncating continuation]* -> plan -> scan(registrations) -> their index -> size -> scans -> emit.
 // The stream moves only when the call has succeeded.
-bool run_mlfilter_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) {
-    (void) garbage;                              // the decoder's loop simply ends at what it refuses: no clean-end check (:847-879)
-    MlFilterState *m = f->mlfilter;
+bool MlFilterState::run(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool) {
+    // (`garbage` is not read: the decoder's loop simply ends at what it refuses, no clean-end check, :847-879)
     uint64_t n = in->n;
     *ret = FLBGPU_FILTER_NOTOUCH;
     f->last_in = 0; f->last_out = 0;
     if (n == 0) return true;
     if (in->bytes > 0xFFFF0000ull) { set_err("filter_multiline: more than 4 GB in one call"); return false; }
-    if (!m->d_words.ensure(sizeof(MlfWords)) || !m->d_misc.ensure(sizeof(MlMisc)) || !m->d_keep.ensure(n * 4) || !m->d_koff.ensure((n + 1) * 8) ||
+    if (!d_words.ensure(sizeof(MlfWords)) || !d_misc.ensure(sizeof(MlMisc)) || !d_keep.ensure(n * 4) || !d_koff.ensure((n + 1) * 8) ||
         !f->d_scan_tmp.ensure(scan_tmp_elems(2 * n + 2) * sizeof(uint64_t)))
         return false;
-    MlfWords *dw = m->d_words.as<MlfWords>(), hw;
+    MlfWords *dw = d_words.as<MlfWords>(), hw;
     uint64_t *tmp = f->d_scan_tmp.as<uint64_t>();
     MlfArgs a;
     memset(&a, 0, sizeof(a));
@@ -245,22 +252,22 @@ bool run_mlfilter_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_c
     std::string pkey;
     bool has_sub = false;
     int nrules = 0;
-    if (!ml_parser_args(m->parser, ma, pkey, has_sub, nrules)) { set_err("filter_multiline: the parser is gone"); return false; }
+    if (!ml_parser_args(parser, ma, pkey, has_sub, nrules)) { set_err("filter_multiline: the parser is gone"); return false; }
     a.data = (const uint8_t *) in->data; a.row_off = in->row_off; a.n = n; a.bytes = in->bytes;
     a.regex = ma.p.type == ML_REGEX ? 1u : 0u; a.type = (uint32_t) ma.p.type; a.match_len = ma.p.match_len;
-    a.has_key = m->has_key ? 1u : 0u; a.key_len = (uint32_t) m->key.size();
-    memcpy(a.key, m->key.data(), m->key.size());
-    a.keep = m->d_keep.as<uint32_t>(); a.koff = m->d_koff.as<uint64_t>(); a.w = dw;
-    a.carry_sec = m->stream.sec; a.carry_nsec = m->stream.nsec;
+    a.has_key = has_key ? 1u : 0u; a.key_len = (uint32_t) key.size();
+    memcpy(a.key, key.data(), key.size());
+    a.keep = d_keep.as<uint32_t>(); a.koff = d_koff.as<uint64_t>(); a.w = dw;
+    a.carry_sec = stream.sec; a.carry_nsec = stream.nsec;
     uint64_t kept = 0;
     auto class_pass = [&]() {
         memset(&hw, 0, sizeof(hw));
         hw.first_bad = ~0ull;
         HIPOK(hipMemcpyAsync(dw, &hw, sizeof(hw), hipMemcpyHostToDevice, st));
         { ProfScope ps(f, st, "k_mlf_class"); launch_mlf_class(a, st); }
-        { ProfScope ps(f, st, "k_scan"); launch_scan(a.keep, a.n, tmp, m->d_koff.as<uint64_t>(), st, nullptr); }
+        { ProfScope ps(f, st, "k_scan"); launch_scan(a.keep, a.n, tmp, d_koff.as<uint64_t>(), st, nullptr); }
         HIPOK(hipMemcpyAsync(&hw, dw, sizeof(hw), hipMemcpyDeviceToHost, st));
-        HIPOK(hipMemcpyAsync(&kept, m->d_koff.as<uint64_t>() + a.n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIPOK(hipMemcpyAsync(&kept, d_koff.as<uint64_t>() + a.n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
         HIPOK(hipStreamSynchronize(st));
         return true;
     };
@@ -275,7 +282,7 @@ bool run_mlfilter_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_c
     std::string why;
     // (the words hold nothing but the metadata count yet) the call is handed back, the stream stays where it was
     auto judged = [&]() {
-        const int j = mlf_judge(hw, m->tot, why);
+        const int j = mlf_judge(hw, tot, why);
         if (j != MLF_GO) set_err("filter_multiline: %s", why.c_str());
         if (j == MLF_HAND_BACK) *ret = -1;
         return j;
@@ -284,31 +291,31 @@ bool run_mlfilter_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_c
     if (kept == 0) return true;
     const uint64_t N = kept + 1;
     a.N = N;
-    if (!m->d_ls.ensure(N * 8) || !m->d_ll.ensure(N * 4) || !m->d_irow.ensure(N * 4) || !m->d_cls.ensure(N) || !m->d_tsec.ensure(N * 4) || !m->d_tnsec.ensure(N * 4) ||
-        !m->d_info.ensure(N * 4) || !m->d_F.ensure(N * 8) || !m->d_sin.ensure(N) || !m->d_act.ensure(N) || !m->d_c.ensure(N * 4) || !m->d_coff.ensure((N + 1) * 8) ||
-        !m->d_head.ensure(N * 4) || !m->d_gidx.ensure((N + 1) * 8) || !m->d_ghead.ensure((N + 1) * 8) || !m->d_ovr.ensure(N * 4) || !m->d_slow.ensure(N * 4) ||
-        !m->d_fs_tmp.ensure(ml_fscan_tmp_bytes(N)) || !m->d_ev.ensure(2 * N * 4) || !m->d_evoff.ensure((2 * N + 1) * 8) || !m->d_regidx.ensure(2 * N * 4) ||
-        !m->d_plen.ensure(N * 4) || !m->d_po.ensure((N + 1) * 8) || !m->d_pre.ensure(N * 4) || !m->d_dup.ensure(N * 4) || !m->d_nrec.ensure(N * 4) ||
-        !m->d_ridx.ensure((N + 1) * 8))
+    if (!d_ls.ensure(N * 8) || !d_ll.ensure(N * 4) || !d_irow.ensure(N * 4) || !d_cls.ensure(N) || !d_tsec.ensure(N * 4) || !d_tnsec.ensure(N * 4) ||
+        !d_info.ensure(N * 4) || !d_F.ensure(N * 8) || !d_sin.ensure(N) || !d_act.ensure(N) || !d_c.ensure(N * 4) || !d_coff.ensure((N + 1) * 8) ||
+        !d_head.ensure(N * 4) || !d_gidx.ensure((N + 1) * 8) || !d_ghead.ensure((N + 1) * 8) || !d_ovr.ensure(N * 4) || !d_slow.ensure(N * 4) ||
+        !d_fs_tmp.ensure(ml_fscan_tmp_bytes(N)) || !d_ev.ensure(2 * N * 4) || !d_evoff.ensure((2 * N + 1) * 8) || !d_regidx.ensure(2 * N * 4) ||
+        !d_plen.ensure(N * 4) || !d_po.ensure((N + 1) * 8) || !d_pre.ensure(N * 4) || !d_dup.ensure(N * 4) || !d_nrec.ensure(N * 4) ||
+        !d_ridx.ensure((N + 1) * 8))
         return false;
-    a.ls = m->d_ls.as<uint64_t>(); a.ll = m->d_ll.as<uint32_t>(); a.irow = m->d_irow.as<uint32_t>(); a.cls = m->d_cls.as<uint8_t>();
-    a.tsec = m->d_tsec.as<uint32_t>(); a.tnsec = m->d_tnsec.as<uint32_t>(); a.info = m->d_info.as<uint32_t>(); a.F = m->d_F.as<uint64_t>();
-    a.act = m->d_act.as<uint8_t>(); a.c = m->d_c.as<uint32_t>(); a.coff = m->d_coff.as<uint64_t>(); a.head = m->d_head.as<uint32_t>();
-    a.gidx = m->d_gidx.as<uint64_t>(); a.ghead = m->d_ghead.as<uint64_t>();
-    a.ev = m->d_ev.as<uint32_t>(); a.evoff = m->d_evoff.as<uint64_t>(); a.regidx = m->d_regidx.as<uint32_t>();
-    a.plen = m->d_plen.as<uint32_t>(); a.po = m->d_po.as<uint64_t>(); a.pre = m->d_pre.as<uint32_t>(); a.dup = m->d_dup.as<uint32_t>();
-    a.nrec = m->d_nrec.as<uint32_t>(); a.ridx = m->d_ridx.as<uint64_t>();
+    a.ls = d_ls.as<uint64_t>(); a.ll = d_ll.as<uint32_t>(); a.irow = d_irow.as<uint32_t>(); a.cls = d_cls.as<uint8_t>();
+    a.tsec = d_tsec.as<uint32_t>(); a.tnsec = d_tnsec.as<uint32_t>(); a.info = d_info.as<uint32_t>(); a.F = d_F.as<uint64_t>();
+    a.act = d_act.as<uint8_t>(); a.c = d_c.as<uint32_t>(); a.coff = d_coff.as<uint64_t>(); a.head = d_head.as<uint32_t>();
+    a.gidx = d_gidx.as<uint64_t>(); a.ghead = d_ghead.as<uint64_t>();
+    a.ev = d_ev.as<uint32_t>(); a.evoff = d_evoff.as<uint64_t>(); a.regidx = d_regidx.as<uint32_t>();
+    a.plen = d_plen.as<uint32_t>(); a.po = d_po.as<uint64_t>(); a.pre = d_pre.as<uint32_t>(); a.dup = d_dup.as<uint32_t>();
+    a.nrec = d_nrec.as<uint32_t>(); a.ridx = d_ridx.as<uint64_t>();
     { ProfScope ps(f, st, "k_mlf_items"); launch_mlf_items(a, st); }
     // the multiline core on these items: item count N through koff[nl] + 1 with nl = 0, no carried bytes, every group closed by the flush
-    MlMisc *dm = m->d_misc.as<MlMisc>(), hm;
+    MlMisc *dm = d_misc.as<MlMisc>(), hm;
     memset(&hm, 0, sizeof(hm));
     ma.p.has_key_content = 1;                    // breakline_prepare adds nothing while key_content is set
-    ma.text = a.data; ma.bytes = in->bytes; ma.nl_pos = nullptr; ma.nl = 0; ma.koff = m->d_koff.as<uint64_t>() + n;
+    ma.text = a.data; ma.bytes = in->bytes; ma.nl_pos = nullptr; ma.nl = 0; ma.koff = d_koff.as<uint64_t>() + n;
     ma.skip_empty_lines = 0; ma.flush_all = 1; ma.NB = N;
-    ma.ls = a.ls; ma.ll = a.ll; ma.info = a.info; ma.F = a.F; ma.sin = m->d_sin.as<uint8_t>(); ma.act = m->d_act.as<uint8_t>();
-    ma.c = m->d_c.as<uint32_t>(); ma.coff = a.coff; ma.head = m->d_head.as<uint32_t>(); ma.gidx = a.gidx; ma.ghead = m->d_ghead.as<uint64_t>();
-    ma.ovr = m->d_ovr.as<uint32_t>(); ma.slow = m->d_slow.as<uint32_t>();
-    ma.carry = m->d_carry.as<uint8_t>(); ma.carry_len = 0; ma.carry_tail = MLT_EMPTY; ma.carry_state = m->stream.state; ma.carry_trunc = 0;
+    ma.ls = a.ls; ma.ll = a.ll; ma.info = a.info; ma.F = a.F; ma.sin = d_sin.as<uint8_t>(); ma.act = d_act.as<uint8_t>();
+    ma.c = d_c.as<uint32_t>(); ma.coff = a.coff; ma.head = d_head.as<uint32_t>(); ma.gidx = a.gidx; ma.ghead = d_ghead.as<uint64_t>();
+    ma.ovr = d_ovr.as<uint32_t>(); ma.slow = d_slow.as<uint32_t>();
+    ma.carry = d_carry.as<uint8_t>(); ma.carry_len = 0; ma.carry_tail = MLT_EMPTY; ma.carry_state = stream.state; ma.carry_trunc = 0;
     ma.misc = dm;
     HIPOK(hipMemsetAsync(dm, 0, sizeof(MlMisc), st));
     HIPOK(hipMemsetAsync(ma.ovr, 0xFF, N * 4, st));
@@ -318,10 +325,10 @@ bool run_mlfilter_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_c
     for (uint64_t round = 0;; round++) {
         // one truncating continuation is settled per round, exactly as flbgpu_ml_append_dev does (ml.cpp)
         launch_ml_reset(dm, st);
-        launch_ml_fscan(ma.F, N, ma.p.type == ML_REGEX ? m->stream.state : (uint32_t) MLT_EMPTY, ma.sin, m->d_fs_tmp.p, &dm->final_state, st);
+        launch_ml_fscan(ma.F, N, ma.p.type == ML_REGEX ? stream.state : (uint32_t) MLT_EMPTY, ma.sin, d_fs_tmp.p, &dm->final_state, st);
         { ProfScope ps(f, st, "k_ml_act"); launch_ml_act(ma, st); }
-        launch_scan(ma.c, N, tmp, m->d_coff.as<uint64_t>(), st);
-        launch_scan(ma.head, N, tmp, m->d_gidx.as<uint64_t>(), st);
+        launch_scan(ma.c, N, tmp, d_coff.as<uint64_t>(), st);
+        launch_scan(ma.head, N, tmp, d_gidx.as<uint64_t>(), st);
         launch_ml_ghead(ma, st);
         if (may_truncate) launch_ml_trunc(ma, st);
         HIPOK(hipMemcpyAsync(&hm, dm, sizeof(hm), hipMemcpyDeviceToHost, st));
@@ -335,28 +342,28 @@ bool run_mlfilter_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_c
         launch_ml_override(ma, hm.trunc_k, st);
     }
     { ProfScope ps(f, st, "k_mlf_plan"); launch_mlf_plan(a, st); }
-    launch_scan(a.ev, 2 * N, tmp, m->d_evoff.as<uint64_t>(), st);
+    launch_scan(a.ev, 2 * N, tmp, d_evoff.as<uint64_t>(), st);
     launch_mlf_regidx(a, st);
     { ProfScope ps(f, st, "k_mlf_size"); launch_mlf_size(a, st); }
-    launch_scan(a.plen, N, tmp, m->d_po.as<uint64_t>(), st);
-    launch_scan(a.nrec, N, tmp, m->d_ridx.as<uint64_t>(), st);
+    launch_scan(a.plen, N, tmp, d_po.as<uint64_t>(), st);
+    launch_scan(a.nrec, N, tmp, d_ridx.as<uint64_t>(), st);
     uint64_t total = 0, R = 0;
-    HIPOK(hipMemcpyAsync(&total, m->d_po.as<uint64_t>() + N, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIPOK(hipMemcpyAsync(&R, m->d_ridx.as<uint64_t>() + N, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIPOK(hipMemcpyAsync(&total, d_po.as<uint64_t>() + N, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    HIPOK(hipMemcpyAsync(&R, d_ridx.as<uint64_t>() + N, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIPOK(hipMemcpyAsync(&hw, dw, sizeof(hw), hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
     { const int j = judged(); if (j != MLF_GO) return j == MLF_HAND_BACK; }
-    if (!f->d_out.ensure(total + 16) || !m->d_rows.ensure((R + 1) * 8)) return false;
-    a.out = f->d_out.as<uint8_t>(); a.rows_out = m->d_rows.as<uint64_t>();
+    if (!f->d_out.ensure(total + 16) || !d_rows.ensure((R + 1) * 8)) return false;
+    a.out = f->d_out.as<uint8_t>(); a.rows_out = d_rows.as<uint64_t>();
     { ProfScope ps(f, st, "k_mlf_emit"); launch_mlf_emit(a, st); }
     HIPOK(hipMemcpyAsync(&hw, dw, sizeof(hw), hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
     if (judged() != MLF_GO) return false;
     // the stream after the call
-    mlf_commit(m->stream, m->tot, ma.p.type == ML_REGEX, hm.final_state, hw, kept);
+    mlf_commit(stream, tot, ma.p.type == ML_REGEX, hm.final_state, hw, kept);
     f->last_in = kept; f->last_out = R;
     if (total == 0) return true;
-    out->data = f->d_out.p; out->row_off = m->d_rows.as<uint64_t>(); out->n = R; out->bytes = total;
+    out->data = f->d_out.p; out->row_off = d_rows.as<uint64_t>(); out->n = R; out->bytes = total;
     *ret = FLBGPU_FILTER_MODIFIED;
     return true;
 }

@@ -1,6 +1,6 @@
 // modify.cpp -- filter_modify (plugins/filter_modify/modify.c): the configuration as setup() reads it (:141-519), the device
 // program behind it, and one cb_modify_filter call on a device chunk (:1486-1578).  The per-record work is modify_kernels.inc.
-#include "host_int.hpp"
+#include "filter_host.hpp"
 #include "mod.hpp"
 
 using namespace flbgpu;
@@ -66,13 +66,6 @@ struct MItem {
     int ra;                     // 0 never finds a value, 1 a key (DevKey below)
     DevKey key;
 };
-
-std::string hexs(const std::string &s) {
-    static const char *hx = "0123456789abcdef";
-    std::string o;
-    for (unsigned char c : s) { o.push_back(hx[c >> 4]); o.push_back(hx[c & 15]); }
-    return o;
-}
 
 // flb_regex_create's verdict; exec: the pattern runs per record and has to be a regular expression the device runs
 bool check_rx(const std::string &pat, bool exec, std::string &why, rx::Program *prog_out) {
@@ -218,9 +211,12 @@ std::string describe(const std::vector<MItem> &items) {
     return d;
 }
 
-}  // namespace
+bool front(int nprops, const char *const *names, const char *const *values, std::vector<MItem> &items) {
+    return parse_front("modify", nprops, names, values, [&](std::string &why) { return parse_program(nprops, names, values, items, why); });
+}
 
-struct ModState {
+struct ModState : FilterState {
+    struct Words { unsigned long long first_bad, counts[5], arena_top; };
     std::vector<ModRule> rules;
     std::vector<ModCond> conds;
     std::vector<DevKey> keys;
@@ -228,27 +224,19 @@ struct ModState {
     std::string str;
     uint32_t true_off = 0, false_off = 0;
     int grow = 0;
-    DevBuf d_rules, d_conds, d_keys, d_rx, d_str, d_words, d_arena, d_mod;
-    PinnedBuf hp_words;
+    ScopedDevBuf d_rules, d_conds, d_keys, d_rx, d_str, d_arena;
+    CallWords<Words> words;
     uint64_t arena_cap = 0;
     uint64_t overread = 0;      // records whose prefix test ran past the record (counted difference, DESIGN)
+    bool run(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) override;
 };
 
-void mod_state_destroy(ModState *m) {
-    if (!m) return;
-    DevBuf *all[] = {&m->d_rules, &m->d_conds, &m->d_keys, &m->d_rx, &m->d_str, &m->d_words, &m->d_arena, &m->d_mod};
-    for (auto *b : all) b->release();
-    m->hp_words.release();
-    delete m;
-}
+}  // namespace
 
 extern "C" int flbgpu_modify_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap) {
     std::vector<MItem> items;
-    std::string why;
-    if (nprops < 0 || (nprops > 0 && (!names || !values))) { set_err("filter_modify: bad arguments"); return -1; }
-    if (!parse_program(nprops, names, values, items, why)) { set_err("filter_modify: %s", why.c_str()); return -1; }
-    const std::string d = describe(items);
-    if (desc && cap) { const size_t n = d.size() < cap - 1 ? d.size() : cap - 1; memcpy(desc, d.data(), n); desc[n] = 0; }
+    if (!front(nprops, names, values, items)) return -1;
+    put_desc(desc, cap, describe(items));
     return 0;
 }
 
@@ -267,21 +255,13 @@ static bool add_rx(ModState *m, flbgpu_filter *f, const std::string &pat, int *i
     return true;
 }
 
-template <class T> static bool upload_vec(DevBuf &b, const std::vector<T> &v) {
-    if (!b.ensure(v.size() * sizeof(T) + 16)) return false;
-    if (!v.empty()) HIPOK(hipMemcpy(b.p, v.data(), v.size() * sizeof(T), hipMemcpyHostToDevice));
-    return true;
-}
-
 extern "C" flbgpu_filter *flbgpu_filter_modify_create(int nprops, const char *const *names, const char *const *values) {
     std::vector<MItem> items;
-    std::string why;
-    if (nprops < 0 || (nprops > 0 && (!names || !values))) { set_err("filter_modify: bad arguments"); return nullptr; }
-    if (!parse_program(nprops, names, values, items, why)) { set_err("filter_modify: %s", why.c_str()); return nullptr; }
+    if (!front(nprops, names, values, items)) return nullptr;
     auto *f = new flbgpu_filter();
     f->kind = F_MODIFY;
     auto *m = new ModState();
-    f->mod = m;
+    f->state = m;
     auto add_str = [&](const std::string &s) { const uint32_t o = (uint32_t) m->str.size(); m->str += s; return o; };
     m->true_off = add_str("true");
     m->false_off = add_str("false");
@@ -307,96 +287,84 @@ extern "C" flbgpu_filter *flbgpu_filter_modify_create(int nprops, const char *co
             m->rules.push_back(r);
         }
     }
-    if (!filter_common_init(f) || !upload_vec(m->d_rules, m->rules) || !upload_vec(m->d_conds, m->conds) || !upload_vec(m->d_keys, m->keys) ||
-        !upload_vec(m->d_rx, m->rx) || !upload_vec(m->d_str, std::vector<char>(m->str.begin(), m->str.end()))) {
+    if (!filter_common_init(f) || !upload(m->d_rules, m->rules) || !upload(m->d_conds, m->conds) || !upload(m->d_keys, m->keys) ||
+        !upload(m->d_rx, m->rx) || !upload(m->d_str, m->str.data(), m->str.size())) {
         delete f;
         return nullptr;
     }
     return f;
 }
 
-extern "C" uint64_t flbgpu_modify_overread(flbgpu_filter *f) { return f && f->kind == F_MODIFY && f->mod ? f->mod->overread : 0; }
+extern "C" uint64_t flbgpu_modify_overread(flbgpu_filter *f) {
+    auto *m = state_of<ModState>(f, F_MODIFY);
+    return m ? m->overread : 0;
+}
 
 constexpr uint64_t MOD_ARENA_INIT = 1u << 16;      // entries (512 KB): the arena a filter keeps between calls
 
 // cb_modify_filter (:1486-1578) on a device chunk: MODIFIED only when a record was rebuilt AND the decoder reached the end of the chunk
-bool run_modify_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) {
-    ModState *m = f->mod;
+bool ModState::run(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) {
     const uint64_t n = in->n;
     *ret = FLBGPU_FILTER_NOTOUCH;
     f->last_in = 0; f->last_out = 0;
     if (n == 0) return true;
-    struct Words { unsigned long long first_bad, counts[5], arena_top; };
-    if (!m->d_words.ensure(sizeof(Words)) || !m->hp_words.ensure(sizeof(Words) + sizeof(uint64_t))) return false;
-    if (!f->d_len.ensure(n * sizeof(uint32_t)) || !f->d_off.ensure((n + 1) * sizeof(uint64_t)) ||
-        !f->d_scan_tmp.ensure(scan_tmp_elems(n) * sizeof(uint64_t)))
-        return false;
-    if (m->arena_cap == 0) {
-        m->arena_cap = MOD_ARENA_INIT;
-        if (!m->d_arena.ensure(m->arena_cap * sizeof(uint64_t))) return false;
+    if (!words.ensure() || !ensure_row_columns(f, n)) return false;
+    if (arena_cap == 0) {
+        arena_cap = MOD_ARENA_INIT;
+        if (!d_arena.ensure(arena_cap * sizeof(uint64_t))) return false;
     }
     // an arena grown for this call's wide maps is handed back when the call ends (every return path)
     struct ArenaTrim {
         ModState *m;
         ~ArenaTrim() { if (m->arena_cap > MOD_ARENA_INIT) { m->d_arena.release(); m->arena_cap = 0; } }
-    } trim{m};
-    Words *dw = m->d_words.as<Words>();
-    Words &hw = *m->hp_words.as<Words>();
-    uint64_t &total = *(uint64_t *) (m->hp_words.as<uint8_t>() + sizeof(Words));
+    } trim{this};
+    Words *dw = words.dev();
+    Words &hw = words.host();
     ModArgs a;
     memset(&a, 0, sizeof(a));
     a.data = (const uint8_t *) in->data; a.row_off = in->row_off; a.n = n;
-    a.rules = m->d_rules.as<ModRule>(); a.nrules = (int) m->rules.size();
-    a.conds = m->d_conds.as<ModCond>(); a.nconds = (int) m->conds.size();
-    a.keys = m->d_keys.as<DevKey>(); a.rx = m->d_rx.as<GrepRule>(); a.str = m->d_str.as<uint8_t>();
-    a.true_off = m->true_off; a.false_off = m->false_off; a.grow = m->grow;
+    a.rules = d_rules.as<ModRule>(); a.nrules = (int) rules.size();
+    a.conds = d_conds.as<ModCond>(); a.nconds = (int) conds.size();
+    a.keys = d_keys.as<DevKey>(); a.rx = d_rx.as<GrepRule>(); a.str = d_str.as<uint8_t>();
+    a.true_off = true_off; a.false_off = false_off; a.grow = grow;
     a.len = f->d_len.as<uint32_t>();
     a.first_bad = &dw->first_bad; a.counts = dw->counts; a.arena_top = &dw->arena_top;
+    // first_bad: what the words start from -- nothing refused yet, or, for the pass in front of a decoder error, that record
+    auto size_pass = [&](const char *name, unsigned long long first_bad) {
+        return words.pass(f, st, name, [&](Words &w) { memset(&w, 0, sizeof(w)); w.first_bad = first_bad; }, [&] { launch_modify(a, false, st); });
+    };
     for (int attempt = 0;; attempt++) {
-        memset(&hw, 0, sizeof(hw));
-        hw.first_bad = ~0ull;
-        a.arena = m->d_arena.as<uint64_t>(); a.arena_cap = m->arena_cap;
-        HIPOK(hipMemcpyAsync(dw, &hw, sizeof(hw), hipMemcpyHostToDevice, st));
-        { ProfScope ps(f, st, "k_modify(size)"); launch_modify(a, false, st); }
-        HIPOK(hipMemcpyAsync(&hw, dw, sizeof(hw), hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
+        a.arena = d_arena.as<uint64_t>(); a.arena_cap = arena_cap;
+        if (!size_pass("k_modify(size)", ~0ull)) return false;
         if (hw.counts[4] >> 32) { set_err("filter_modify: a record's output is larger than 4 GB"); return false; }
         if ((hw.counts[4] & 0xFFFFFFFFull) == 0) break;
         // rows with more entries than a lane's LDS list holds: their lists did not all fit in the arena -- grow it, size again
         if (attempt > 0) { set_err("filter_modify: the entry arena did not grow"); return false; }
-        m->d_arena.release();
-        m->arena_cap = hw.counts[3] + hw.counts[3] / 4 + 1024;
-        if (!m->d_arena.ensure(m->arena_cap * sizeof(uint64_t))) return false;
+        d_arena.release();
+        arena_cap = hw.counts[3] + hw.counts[3] / 4 + 1024;
+        if (!d_arena.ensure(arena_cap * sizeof(uint64_t))) return false;
     }
     if (hw.first_bad != ~0ull && hw.first_bad > 0) {
         // the reference's decoder loop stops at the first bad record: the records it decoded, and its prefix tests, are the ones in
         // front of it -- the size pass again over those rows only (a call that ends in NOTOUCH anyway)
         const unsigned long long fb = hw.first_bad;
-        memset(&hw, 0, sizeof(hw));
-        hw.first_bad = fb;
         a.n = fb;
-        HIPOK(hipMemcpyAsync(dw, &hw, sizeof(hw), hipMemcpyHostToDevice, st));
-        { ProfScope ps(f, st, "k_modify(size, in front of a decoder error)"); launch_modify(a, false, st); }
-        HIPOK(hipMemcpyAsync(&hw, dw, sizeof(hw), hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
+        if (!size_pass("k_modify(size, in front of a decoder error)", fb)) return false;
         hw.first_bad = fb;
     }
     else if (hw.first_bad == 0) hw.counts[0] = hw.counts[2] = 0;
     f->last_in = hw.counts[0];
     f->last_out = hw.counts[0];
-    m->overread += hw.counts[2];
+    overread += hw.counts[2];
     // a decoder error anywhere (or a tail that is not a clean end) and the reference answers NOTOUCH (:1549-1571); so does a call
     // that rebuilt nothing
     if (hw.first_bad != ~0ull || garbage || hw.counts[1] == 0) return true;
-    { ProfScope ps(f, st, "k_scan"); launch_scan(a.len, n, f->d_scan_tmp.as<uint64_t>(), f->d_off.as<uint64_t>(), st, nullptr); }
-    HIPOK(hipMemcpyAsync(&total, f->d_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
-    if (!f->d_out.ensure(total + 16)) return false;
+    if (!scan_lengths(f, st, a.len, n, &words.total())) return false;
     HIPOK(hipMemsetAsync(&dw->arena_top, 0, sizeof(dw->arena_top), st));
     a.out_off = f->d_off.as<uint64_t>(); a.out = f->d_out.as<uint8_t>();
     { ProfScope ps(f, st, "k_modify(emit)"); launch_modify(a, true, st); }
     HIPOK(hipStreamSynchronize(st));
-    out->data = f->d_out.p; out->row_off = f->d_off.as<uint64_t>(); out->n = n; out->bytes = total;
+    set_out(f, out, n, words.total());
     *ret = FLBGPU_FILTER_MODIFIED;
     return true;
 }

@@ -1,7 +1,7 @@
 // nest.cpp -- filter_nest (plugins/filter_nest/nest.c): the configuration as configure() reads it (:57-175, behind the config map of
 // :729-761), the device program behind it, and one cb_nest_filter call on a device chunk (:631-717).  The per-record work is
 // nest_kernels.inc.
-#include "host_int.hpp"
+#include "filter_host.hpp"
 #include "nest.hpp"
 
 using namespace flbgpu;
@@ -17,13 +17,6 @@ struct NProgram {
     bool add = false, remove = false;
     std::string prefix;
 };
-
-std::string hexs(const std::string &s) {
-    static const char *hx = "0123456789abcdef";
-    std::string o;
-    for (unsigned char c : s) { o.push_back(hx[c >> 4]); o.push_back(hx[c & 15]); }
-    return o;
-}
 
 size_t pad4(size_t n) { return (n + 3) & ~(size_t) 3; }
 
@@ -86,43 +79,36 @@ void put_bytes(std::vector<uint32_t> &table, const std::string &s) {
     }
 }
 
-}  // namespace
+bool front(int nprops, const char *const *names, const char *const *values, NProgram &pg) {
+    return parse_front("nest", nprops, names, values, [&](std::string &why) { return parse_program(nprops, names, values, pg, why); });
+}
 
-struct NestState {
+struct NestState : FilterState {
+    struct Words { unsigned long long first_bad, counts[6]; };
     int op = 0, nwild = 0, has_key = 0, pfx = NEST_PFX_NONE;
     uint32_t table_bytes = 0, key_off = 0, key_len = 0, pfx_off = 0, pfx_len = 0;
     uint64_t modified = 0, overread = 0, undefined = 0, big = 0;        // since the filter was created (flbgpu_nest_counters)
-    DevBuf d_table, d_words, d_mode;
-    PinnedBuf hp_words;
+    ScopedDevBuf d_table, d_mode;
+    CallWords<Words> words;
+    bool run(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) override;
 };
 
-void nest_state_destroy(NestState *m) {
-    if (!m) return;
-    DevBuf *all[] = {&m->d_table, &m->d_words, &m->d_mode};
-    for (auto *b : all) b->release();
-    m->hp_words.release();
-    delete m;
-}
+}  // namespace
 
 extern "C" int flbgpu_nest_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap) {
     NProgram pg;
-    std::string why;
-    if (nprops < 0 || (nprops > 0 && (!names || !values))) { set_err("filter_nest: bad arguments"); return -1; }
-    if (!parse_program(nprops, names, values, pg, why)) { set_err("filter_nest: %s", why.c_str()); return -1; }
-    const std::string d = describe(pg);
-    if (desc && cap) { const size_t n = d.size() < cap - 1 ? d.size() : cap - 1; memcpy(desc, d.data(), n); desc[n] = 0; }
+    if (!front(nprops, names, values, pg)) return -1;
+    put_desc(desc, cap, describe(pg));
     return 0;
 }
 
 extern "C" flbgpu_filter *flbgpu_filter_nest_create(int nprops, const char *const *names, const char *const *values) {
     NProgram pg;
-    std::string why;
-    if (nprops < 0 || (nprops > 0 && (!names || !values))) { set_err("filter_nest: bad arguments"); return nullptr; }
-    if (!parse_program(nprops, names, values, pg, why)) { set_err("filter_nest: %s", why.c_str()); return nullptr; }
+    if (!front(nprops, names, values, pg)) return nullptr;
     auto *f = new flbgpu_filter();
     f->kind = F_NEST;
     auto *m = new NestState();
-    f->nest = m;
+    f->state = m;
     m->op = pg.op;
     m->nwild = (int) pg.wild.size();
     m->has_key = pg.has_key ? 1 : 0;
@@ -139,53 +125,35 @@ extern "C" flbgpu_filter *flbgpu_filter_nest_create(int nprops, const char *cons
     m->pfx_off = (uint32_t) (table.size() * 4); m->pfx_len = (uint32_t) pg.prefix.size();
     put_bytes(table, pg.prefix);
     m->table_bytes = (uint32_t) (table.size() * 4);
-    if (!filter_common_init(f) || !m->d_table.ensure(m->table_bytes + 16) ||
-        (m->table_bytes && hipMemcpy(m->d_table.p, table.data(), m->table_bytes, hipMemcpyHostToDevice) != hipSuccess)) {
-        delete f;
-        return nullptr;
-    }
+    if (!filter_common_init(f) || !upload(m->d_table, table)) { delete f; return nullptr; }
     return f;
 }
 
 extern "C" void flbgpu_nest_counters(flbgpu_filter *f, uint64_t out[4]) {
     out[0] = out[1] = out[2] = out[3] = 0;
-    if (!f || f->kind != F_NEST || !f->nest) return;
-    out[0] = f->nest->modified; out[1] = f->nest->overread; out[2] = f->nest->undefined; out[3] = f->nest->big;
+    if (auto *m = state_of<NestState>(f, F_NEST)) { out[0] = m->modified; out[1] = m->overread; out[2] = m->undefined; out[3] = m->big; }
 }
 
 // cb_nest_filter (:631-717) on a device chunk.  A decoder error ends the loop and the call answers with what was encoded in front of
 // it (:671-696) -- so undecodable bytes behind the rows (`garbage`) change nothing here.  MODIFIED whenever a byte came out (:698-711).
-bool run_nest_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) {
-    (void) garbage;
-    NestState *m = f->nest;
+bool NestState::run(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool) {
     const uint64_t n = in->n;
     *ret = FLBGPU_FILTER_NOTOUCH;
     f->last_in = 0; f->last_out = 0;
     if (n == 0) return true;
-    struct Words { unsigned long long first_bad, counts[6]; };
-    if (!m->d_words.ensure(sizeof(Words)) || !m->hp_words.ensure(sizeof(Words) + sizeof(uint64_t))) return false;
-    if (!f->d_len.ensure(n * sizeof(uint32_t)) || !m->d_mode.ensure(n) || !f->d_off.ensure((n + 1) * sizeof(uint64_t)) ||
-        !f->d_scan_tmp.ensure(scan_tmp_elems(n) * sizeof(uint64_t)))
-        return false;
-    Words *dw = m->d_words.as<Words>();
-    Words &hw = *m->hp_words.as<Words>();
-    uint64_t &total = *(uint64_t *) (m->hp_words.as<uint8_t>() + sizeof(Words));
+    if (!words.ensure() || !ensure_row_columns(f, n) || !d_mode.ensure(n)) return false;
+    Words *dw = words.dev();
+    Words &hw = words.host();
     NestArgs a;
     memset(&a, 0, sizeof(a));
     a.data = (const uint8_t *) in->data; a.row_off = in->row_off; a.n = n;
-    a.table = m->d_table.as<uint32_t>(); a.table_bytes = m->table_bytes;
-    a.op = m->op; a.nwild = m->nwild; a.has_key = m->has_key; a.key_off = m->key_off; a.key_len = m->key_len;
-    a.pfx = m->pfx; a.pfx_off = m->pfx_off; a.pfx_len = m->pfx_len;
-    a.len = f->d_len.as<uint32_t>(); a.mode = m->d_mode.as<uint8_t>();
+    a.table = d_table.as<uint32_t>(); a.table_bytes = table_bytes;
+    a.op = op; a.nwild = nwild; a.has_key = has_key; a.key_off = key_off; a.key_len = key_len;
+    a.pfx = pfx; a.pfx_off = pfx_off; a.pfx_len = pfx_len;
+    a.len = f->d_len.as<uint32_t>(); a.mode = d_mode.as<uint8_t>();
     a.first_bad = &dw->first_bad; a.counts = dw->counts;
     auto size_pass = [&](const char *name) {
-        memset(&hw, 0, sizeof(hw));
-        hw.first_bad = ~0ull;
-        HIPOK(hipMemcpyAsync(dw, &hw, sizeof(hw), hipMemcpyHostToDevice, st));
-        { ProfScope ps(f, st, name); launch_nest(a, false, st); }
-        HIPOK(hipMemcpyAsync(&hw, dw, sizeof(hw), hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
-        return true;
+        return words.pass(f, st, name, [](Words &w) { memset(&w, 0, sizeof(w)); w.first_bad = ~0ull; }, [&] { launch_nest(a, false, st); });
     };
     if (!size_pass("k_nest(size)")) return false;
     const unsigned long long fb = hw.first_bad;
@@ -197,19 +165,16 @@ bool run_nest_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk
         a.n = fb;
         if (!size_pass("k_nest(size, in front of a decoder error)")) return false;
     }
-    m->modified += hw.counts[2]; m->big += hw.counts[3]; m->overread += hw.counts[4]; m->undefined += hw.counts[5];
+    modified += hw.counts[2]; big += hw.counts[3]; overread += hw.counts[4]; undefined += hw.counts[5];
     if (hw.counts[3]) { set_err("filter_nest: a record's output is larger than 4 GB"); return false; }
     f->last_in = hw.counts[0];
     f->last_out = hw.counts[0];
     if (hw.counts[1] == 0) return true;                                 // nothing in the encoder: NOTOUCH (:706-711)
-    { ProfScope ps(f, st, "k_scan"); launch_scan(a.len, n, f->d_scan_tmp.as<uint64_t>(), f->d_off.as<uint64_t>(), st, nullptr); }
-    HIPOK(hipMemcpyAsync(&total, f->d_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
-    if (!f->d_out.ensure(total + 16)) return false;
+    if (!scan_lengths(f, st, a.len, n, &words.total())) return false;
     a.out_off = f->d_off.as<uint64_t>(); a.out = f->d_out.as<uint8_t>();
     { ProfScope ps(f, st, "k_nest(emit)"); launch_nest(a, true, st); }
     HIPOK(hipStreamSynchronize(st));
-    out->data = f->d_out.p; out->row_off = f->d_off.as<uint64_t>(); out->n = n; out->bytes = total;
+    set_out(f, out, n, words.total());
     f->last_out = hw.counts[1];
     *ret = FLBGPU_FILTER_MODIFIED;
     return true;

@@ -1,7 +1,7 @@
 // recmod.cpp -- filter_record_modifier (plugins/filter_record_modifier/filter_modifier.c): the configuration as configure() reads it
 // (:69-155, behind the config map of :499-529), the device program behind it, and one cb_modifier_filter call on a device chunk
 // (:298-486).  The per-record work is recmod_kernels.inc.
-#include "host_int.hpp"
+#include "filter_host.hpp"
 #include "recmod.hpp"
 
 using namespace flbgpu;
@@ -73,13 +73,6 @@ struct RProgram {
     std::vector<std::pair<std::string, std::string>> records;
 };
 
-std::string hexs(const std::string &s) {
-    static const char *hx = "0123456789abcdef";
-    std::string o;
-    for (unsigned char c : s) { o.push_back(hx[c >> 4]); o.push_back(hx[c & 15]); }
-    return o;
-}
-
 // the config map (:499-529) and configure() (:69-155) over the properties in configuration order
 bool parse_program(int nprops, const char *const *names, const char *const *values, RProgram &pg, std::string &why) {
     std::vector<RKey> remove, allow, white;
@@ -137,42 +130,35 @@ void pack_str(std::vector<uint8_t> &o, const std::string &s) {
     o.insert(o.end(), s.begin(), s.end());
 }
 
-}  // namespace
+bool front(int nprops, const char *const *names, const char *const *values, RProgram &pg) {
+    return parse_front("record_modifier", nprops, names, values, [&](std::string &why) { return parse_program(nprops, names, values, pg, why); });
+}
 
-struct RecmodState {
+struct RecmodState : FilterState {
+    struct Words { unsigned long long first_bad, first_wide, counts[4]; };
     int list = RECMOD_NONE, nkeys = 0;
     uint32_t nrec = 0, table_bytes = 0, tail_len = 0;
-    DevBuf d_table, d_tail, d_words;
-    PinnedBuf hp_words;
+    ScopedDevBuf d_table, d_tail;
+    CallWords<Words> words;
+    bool run(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) override;
 };
 
-void recmod_state_destroy(RecmodState *m) {
-    if (!m) return;
-    DevBuf *all[] = {&m->d_table, &m->d_tail, &m->d_words};
-    for (auto *b : all) b->release();
-    m->hp_words.release();
-    delete m;
-}
+}  // namespace
 
 extern "C" int flbgpu_record_modifier_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap) {
     RProgram pg;
-    std::string why;
-    if (nprops < 0 || (nprops > 0 && (!names || !values))) { set_err("filter_record_modifier: bad arguments"); return -1; }
-    if (!parse_program(nprops, names, values, pg, why)) { set_err("filter_record_modifier: %s", why.c_str()); return -1; }
-    const std::string d = describe(pg);
-    if (desc && cap) { const size_t n = d.size() < cap - 1 ? d.size() : cap - 1; memcpy(desc, d.data(), n); desc[n] = 0; }
+    if (!front(nprops, names, values, pg)) return -1;
+    put_desc(desc, cap, describe(pg));
     return 0;
 }
 
 extern "C" flbgpu_filter *flbgpu_filter_record_modifier_create(int nprops, const char *const *names, const char *const *values) {
     RProgram pg;
-    std::string why;
-    if (nprops < 0 || (nprops > 0 && (!names || !values))) { set_err("filter_record_modifier: bad arguments"); return nullptr; }
-    if (!parse_program(nprops, names, values, pg, why)) { set_err("filter_record_modifier: %s", why.c_str()); return nullptr; }
+    if (!front(nprops, names, values, pg)) return nullptr;
     auto *f = new flbgpu_filter();
     f->kind = F_RECMOD;
     auto *m = new RecmodState();
-    f->recmod = m;
+    f->state = m;
     m->list = pg.list;
     m->nkeys = (int) pg.keys.size();
     m->nrec = (uint32_t) pg.records.size();
@@ -196,47 +182,29 @@ extern "C" flbgpu_filter *flbgpu_filter_record_modifier_create(int nprops, const
     std::vector<uint8_t> tail;
     for (const auto &r : pg.records) { pack_str(tail, r.first); pack_str(tail, r.second); }
     m->tail_len = (uint32_t) tail.size();
-    if (!filter_common_init(f) || !m->d_table.ensure(m->table_bytes + 16) || !m->d_tail.ensure(tail.size() + 16) ||
-        (m->table_bytes && hipMemcpy(m->d_table.p, table.data(), m->table_bytes, hipMemcpyHostToDevice) != hipSuccess) ||
-        (!tail.empty() && hipMemcpy(m->d_tail.p, tail.data(), tail.size(), hipMemcpyHostToDevice) != hipSuccess)) {
-        delete f;
-        return nullptr;
-    }
+    if (!filter_common_init(f) || !upload(m->d_table, table) || !upload(m->d_tail, tail)) { delete f; return nullptr; }
     return f;
 }
 
 // cb_modifier_filter (:298-486) on a device chunk.  A decoder error ends the loop and the call answers with what was encoded in
 // front of it (:351-353, :469-477) -- so undecodable bytes behind the rows (`garbage`) change nothing here.
-bool run_recmod_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) {
-    (void) garbage;
-    RecmodState *m = f->recmod;
+bool RecmodState::run(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool) {
     const uint64_t n = in->n;
     *ret = FLBGPU_FILTER_NOTOUCH;
     f->last_in = 0; f->last_out = 0;
     if (n == 0) return true;
-    struct Words { unsigned long long first_bad, first_wide, counts[4]; };
-    if (!m->d_words.ensure(sizeof(Words)) || !m->hp_words.ensure(sizeof(Words) + sizeof(uint64_t))) return false;
-    if (!f->d_len.ensure(n * sizeof(uint32_t)) || !f->d_off.ensure((n + 1) * sizeof(uint64_t)) ||
-        !f->d_scan_tmp.ensure(scan_tmp_elems(n) * sizeof(uint64_t)))
-        return false;
-    Words *dw = m->d_words.as<Words>();
-    Words &hw = *m->hp_words.as<Words>();
-    uint64_t &total = *(uint64_t *) (m->hp_words.as<uint8_t>() + sizeof(Words));
+    if (!words.ensure() || !ensure_row_columns(f, n)) return false;
+    Words *dw = words.dev();
+    Words &hw = words.host();
     RecmodArgs a;
     memset(&a, 0, sizeof(a));
     a.data = (const uint8_t *) in->data; a.row_off = in->row_off; a.n = n;
-    a.table = m->d_table.as<uint32_t>(); a.table_bytes = m->table_bytes; a.nkeys = m->nkeys; a.list = m->list;
-    a.nrec = m->nrec; a.tail = m->d_tail.as<uint8_t>(); a.tail_len = m->tail_len;
+    a.table = d_table.as<uint32_t>(); a.table_bytes = table_bytes; a.nkeys = nkeys; a.list = list;
+    a.nrec = nrec; a.tail = d_tail.as<uint8_t>(); a.tail_len = tail_len;
     a.len = f->d_len.as<uint32_t>();
     a.first_bad = &dw->first_bad; a.first_wide = &dw->first_wide; a.counts = dw->counts;
     auto size_pass = [&](const char *name) {
-        memset(&hw, 0, sizeof(hw));
-        hw.first_bad = ~0ull; hw.first_wide = ~0ull;
-        HIPOK(hipMemcpyAsync(dw, &hw, sizeof(hw), hipMemcpyHostToDevice, st));
-        { ProfScope ps(f, st, name); launch_recmod(a, false, st); }
-        HIPOK(hipMemcpyAsync(&hw, dw, sizeof(hw), hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
-        return true;
+        return words.pass(f, st, name, [](Words &w) { memset(&w, 0, sizeof(w)); w.first_bad = ~0ull; w.first_wide = ~0ull; }, [&] { launch_recmod(a, false, st); });
     };
     if (!size_pass("k_recmod(size)")) return false;
     const unsigned long long fb = hw.first_bad;
@@ -258,17 +226,14 @@ bool run_recmod_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chu
     f->last_in = hw.counts[0];
     f->last_out = hw.counts[0];
     // is_modified: a key was removed somewhere, or Record entries were appended to a record; MODIFIED needs a byte in the encoder too
-    const bool is_modified = hw.counts[2] > 0 || (m->nrec > 0 && hw.counts[0] > 0);
+    const bool is_modified = hw.counts[2] > 0 || (nrec > 0 && hw.counts[0] > 0);
     if (!is_modified || hw.counts[1] == 0) return true;
     const uint64_t n_out = hw.counts[1];
-    { ProfScope ps(f, st, "k_scan"); launch_scan(a.len, n, f->d_scan_tmp.as<uint64_t>(), f->d_off.as<uint64_t>(), st, nullptr); }
-    HIPOK(hipMemcpyAsync(&total, f->d_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
-    if (!f->d_out.ensure(total + 16)) return false;
+    if (!scan_lengths(f, st, a.len, n, &words.total())) return false;
     a.out_off = f->d_off.as<uint64_t>(); a.out = f->d_out.as<uint8_t>();
     { ProfScope ps(f, st, "k_recmod(emit)"); launch_recmod(a, true, st); }
     HIPOK(hipStreamSynchronize(st));
-    out->data = f->d_out.p; out->row_off = f->d_off.as<uint64_t>(); out->n = n; out->bytes = total;
+    set_out(f, out, n, words.total());
     f->last_out = n_out;
     *ret = FLBGPU_FILTER_MODIFIED;
     return true;

@@ -1,7 +1,7 @@
 // rtag.cpp -- filter_rewrite_tag (plugins/filter_rewrite_tag/rewrite_tag.c): the configuration as the config map (:590-613) and
 // process_config (:112-190) read it, the device program behind it, and one cb_rewrite_tag_filter call on a device chunk (:425-557)
 // with the emitter's side of it (in_emitter_add_record, :403-420).  The per-record work is rtag_kernels.inc.
-#include "host_int.hpp"
+#include "filter_host.hpp"
 #include "rtag.hpp"
 
 using namespace flbgpu;
@@ -16,13 +16,6 @@ struct RRule {
     std::vector<RaPart> parts;         // NEW_TAG
 };
 struct RProgram { std::vector<RRule> rules; };
-
-std::string hexs(const std::string &s) {
-    static const char *hx = "0123456789abcdef";
-    std::string o;
-    for (unsigned char c : s) { o.push_back(hx[c >> 4]); o.push_back(hx[c & 15]); }
-    return o;
-}
 
 void put_bytes(std::vector<uint32_t> &table, const char *s, size_t n) {
     for (size_t j = 0; j < n; j += 4) {
@@ -193,16 +186,18 @@ std::string describe(const RProgram &pg) {
     return d;
 }
 
-bool bad_args(int nprops, const char *const *names, const char *const *values) { return nprops < 0 || (nprops > 0 && (!names || !values)); }
+bool front(int nprops, const char *const *names, const char *const *values, RProgram &pg) {
+    return parse_front("rewrite_tag", nprops, names, values, [&](std::string &why) { return parse_program(nprops, names, values, pg, why); });
+}
 
-}  // namespace
-
-struct RtagState {
+struct RtagState : FilterState {
+    struct Words { unsigned long long first_bad, max_row, counts[6]; };
+    struct Totals { uint64_t n_emit, tag_bytes, kept_bytes; unsigned long long kept; };
     int nrules = 0, ncaps = 0;
     uint32_t table_bytes = 0, max_vw = 0;                 // max_vw: widest position set of a capture program on the NFA engine (0: none)
-    std::vector<TableBlob *> blobs;
-    DevBuf d_table, d_rules, d_caps, d_words, d_tag, d_rule, d_emit, d_emit_idx, d_taglen, d_tag_off, d_tags, d_table_out, d_spans, d_chk, d_refused;
-    PinnedBuf hp_words;
+    std::vector<std::unique_ptr<TableBlob>> blobs;
+    ScopedDevBuf d_table, d_rules, d_caps, d_tag, d_rule, d_emit, d_emit_idx, d_taglen, d_tag_off, d_tags, d_table_out, d_spans, d_chk, d_refused;
+    CallWords<Words, Totals> words;                       // (on the device, behind the words: the kept records' count of the last scan)
     std::string tag;
     bool tag_dirty = true;
     int (*emit_cb)(void *, const char *, int, const void *, size_t) = nullptr;
@@ -215,37 +210,26 @@ struct RtagState {
     std::vector<uint8_t> h_tags, h_input;
     const uint8_t *input = nullptr;
     uint64_t input_bytes = 0;
+    bool run(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) override;
 };
 
-void rtag_state_destroy(RtagState *m) {
-    if (!m) return;
-    for (auto *b : m->blobs) delete b;
-    DevBuf *all[] = {&m->d_table, &m->d_rules, &m->d_caps, &m->d_words, &m->d_tag, &m->d_rule, &m->d_emit, &m->d_emit_idx, &m->d_taglen, &m->d_tag_off,
-                     &m->d_tags, &m->d_table_out, &m->d_spans, &m->d_chk, &m->d_refused};
-    for (auto *b : all) b->release();
-    m->hp_words.release();
-    delete m;
-}
+}  // namespace
 
 extern "C" int flbgpu_rewrite_tag_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap) {
     RProgram pg;
-    std::string why;
-    if (bad_args(nprops, names, values)) { set_err("filter_rewrite_tag: bad arguments"); return -1; }
-    if (!parse_program(nprops, names, values, pg, why)) { set_err("filter_rewrite_tag: %s", why.c_str()); return -1; }
-    const std::string d = describe(pg);
-    if (desc && cap) { const size_t n = d.size() < cap - 1 ? d.size() : cap - 1; memcpy(desc, d.data(), n); desc[n] = 0; }
+    if (!front(nprops, names, values, pg)) return -1;
+    put_desc(desc, cap, describe(pg));
     return 0;
 }
 
 extern "C" flbgpu_filter *flbgpu_filter_rewrite_tag_create(int nprops, const char *const *names, const char *const *values) {
     RProgram pg;
     std::string why;
-    if (bad_args(nprops, names, values)) { set_err("filter_rewrite_tag: bad arguments"); return nullptr; }
-    if (!parse_program(nprops, names, values, pg, why)) { set_err("filter_rewrite_tag: %s", why.c_str()); return nullptr; }
+    if (!front(nprops, names, values, pg)) return nullptr;
     auto *f = new flbgpu_filter();
     f->kind = F_RTAG;
     auto *m = new RtagState();
-    f->rtag = m;
+    f->state = m;
     m->nrules = (int) pg.rules.size();
     std::vector<uint32_t> table;
     build_table(pg, table);
@@ -257,7 +241,7 @@ extern "C" flbgpu_filter *flbgpu_filter_rewrite_tag_create(int nprops, const cha
         memset(&rules[i], 0, sizeof(GrepRule));
         rx::Program prog;
         auto *b1 = new TableBlob(), *b2 = new TableBlob();
-        m->blobs.push_back(b1); m->blobs.push_back(b2);
+        m->blobs.emplace_back(b1); m->blobs.emplace_back(b2);
         if (!compile_pattern(r, false, prog, why) || !upload_dfa(prog.ascii, *b1, rules[i].dfa) || !upload_utf8(prog, *b2, rules[i].utf8)) {
             if (!why.empty()) set_err("filter_rewrite_tag: %s", why.c_str());
             delete f;
@@ -268,7 +252,7 @@ extern "C" flbgpu_filter *flbgpu_filter_rewrite_tag_create(int nprops, const cha
         RtagCap c;
         memset(&c, 0, sizeof(c));
         auto *b3 = new TableBlob(), *b4 = new TableBlob();
-        m->blobs.push_back(b3); m->blobs.push_back(b4);
+        m->blobs.emplace_back(b3); m->blobs.emplace_back(b4);
         if (!compile_pattern(r, true, cp, why) || !upload_cap(cp.ascii, *b3, c.ascii) || !upload_utf8(cp, *b4, c.utf8)) {
             if (!why.empty()) set_err("filter_rewrite_tag: %s", why.c_str());
             delete f;
@@ -282,38 +266,31 @@ extern "C" flbgpu_filter *flbgpu_filter_rewrite_tag_create(int nprops, const cha
     }
     m->ncaps = (int) caps.size();
     f->rules = rules;                   // (flbgpu_filter_regex_corners reads the match tables' corner counters from here)
-    bool ok = filter_common_init(f) && m->d_table.ensure(m->table_bytes + 16) && m->d_rules.ensure(rules.size() * sizeof(GrepRule) + 16) &&
-              m->d_caps.ensure(caps.size() * sizeof(RtagCap) + 16);
-    ok = ok && hipMemcpy(m->d_table.p, table.data(), m->table_bytes, hipMemcpyHostToDevice) == hipSuccess;
-    ok = ok && (rules.empty() || hipMemcpy(m->d_rules.p, rules.data(), rules.size() * sizeof(GrepRule), hipMemcpyHostToDevice) == hipSuccess);
-    ok = ok && (caps.empty() || hipMemcpy(m->d_caps.p, caps.data(), caps.size() * sizeof(RtagCap), hipMemcpyHostToDevice) == hipSuccess);
-    if (!ok) { delete f; return nullptr; }
+    if (!filter_common_init(f) || !upload(m->d_table, table) || !upload(m->d_rules, rules) || !upload(m->d_caps, caps)) { delete f; return nullptr; }
     return f;
 }
 
 extern "C" void flbgpu_rewrite_tag_set_tag(flbgpu_filter *f, const char *tag, int tag_len) {
-    if (!f || f->kind != F_RTAG || !f->rtag) return;
-    f->rtag->tag.assign(tag && tag_len > 0 ? tag : "", tag && tag_len > 0 ? (size_t) tag_len : 0);
-    f->rtag->tag_dirty = true;
+    auto *m = state_of<RtagState>(f, F_RTAG);
+    if (!m) return;
+    m->tag.assign(tag && tag_len > 0 ? tag : "", tag && tag_len > 0 ? (size_t) tag_len : 0);
+    m->tag_dirty = true;
 }
 
 extern "C" void flbgpu_rewrite_tag_set_emitter(flbgpu_filter *f, int (*emit)(void *ctx, const char *tag, int tag_len, const void *buf, size_t size), void *ctx) {
-    if (!f || f->kind != F_RTAG || !f->rtag) return;
-    f->rtag->emit_cb = emit;
-    f->rtag->emit_ctx = ctx;
+    if (auto *m = state_of<RtagState>(f, F_RTAG)) { m->emit_cb = emit; m->emit_ctx = ctx; }
 }
 
 extern "C" void flbgpu_rewrite_tag_counters(flbgpu_filter *f, uint64_t out[4]) {
     out[0] = out[1] = out[2] = out[3] = 0;
-    if (!f || f->kind != F_RTAG || !f->rtag) return;
-    out[0] = f->rtag->emitted; out[1] = f->rtag->refused; out[2] = f->rtag->mismatch; out[3] = f->rtag->tag_bytes;
+    if (auto *m = state_of<RtagState>(f, F_RTAG)) { out[0] = m->emitted; out[1] = m->refused; out[2] = m->mismatch; out[3] = m->tag_bytes; }
 }
 
 extern "C" int flbgpu_rewrite_tag_emitted(flbgpu_filter *f, flbgpu_rtag_emitted *out) {
     if (!out) return -1;
     memset(out, 0, sizeof(*out));
-    if (!f || f->kind != F_RTAG || !f->rtag) { set_err("filter_rewrite_tag: not a rewrite_tag filter"); return -1; }
-    RtagState *m = f->rtag;
+    RtagState *m = state_of<RtagState>(f, F_RTAG);
+    if (!m) { set_err("filter_rewrite_tag: not a rewrite_tag filter"); return -1; }
     if (!m->on_host) {
         // a device-level call: every emission was taken; the table and the arena come over when somebody asks
         m->h_recs.resize(m->last_n);
@@ -334,8 +311,8 @@ extern "C" int flbgpu_rewrite_tag_emitted(flbgpu_filter *f, flbgpu_rtag_emitted 
 extern "C" int flbgpu_rewrite_tag_emitted_dev(flbgpu_filter *f, flbgpu_rtag_emitted *out) {
     if (!out) return -1;
     memset(out, 0, sizeof(*out));
-    if (!f || f->kind != F_RTAG || !f->rtag) { set_err("filter_rewrite_tag: not a rewrite_tag filter"); return -1; }
-    RtagState *m = f->rtag;
+    RtagState *m = state_of<RtagState>(f, F_RTAG);
+    if (!m) { set_err("filter_rewrite_tag: not a rewrite_tag filter"); return -1; }
     out->count = m->last_n;
     out->recs = m->last_n ? (const flbgpu_rtag_emitted_rec *) m->d_table_out.p : nullptr;
     out->tags = m->last_n ? (const char *) m->d_tags.p : nullptr;
@@ -350,47 +327,38 @@ static_assert(sizeof(RtagEmitted) == sizeof(flbgpu_rtag_emitted_rec), "the emitt
 // scan(kept bytes) -> copy.  The tags come before the compaction because a refusal changes what is kept; a call nobody refuses
 // uploads nothing.  The call hands a buffer on only when a record was emitted (:517-522) AND the decoder's loop ended on a clean end of
 // data (:533-551): the emissions in front of a decoder error have happened all the same.
-bool run_rtag_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) {
-    RtagState *m = f->rtag;
+bool RtagState::run(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) {
     const uint64_t n = in->n;
     *ret = FLBGPU_FILTER_NOTOUCH;
     f->last_in = 0; f->last_out = 0;
-    m->last_n = 0; m->last_tag_bytes = 0; m->on_host = true;
-    m->h_recs.clear(); m->h_tags.clear(); m->input = nullptr; m->input_bytes = 0;
+    last_n = 0; last_tag_bytes = 0; on_host = true;
+    h_recs.clear(); h_tags.clear(); input = nullptr; input_bytes = 0;
     if (n == 0) return true;
-    struct Words { unsigned long long first_bad, max_row, counts[6]; };
-    struct Totals { uint64_t n_emit, tag_bytes, kept_bytes; unsigned long long kept; };
-    if (!m->d_words.ensure(sizeof(Words) + 8) || !m->hp_words.ensure(sizeof(Words) + sizeof(Totals))) return false;
-    if (!m->d_rule.ensure(n * 4) || !m->d_emit.ensure(n * 4) || !m->d_taglen.ensure(n * 4) || !f->d_len.ensure(n * 4) ||
-        !m->d_emit_idx.ensure((n + 1) * 8) || !m->d_tag_off.ensure((n + 1) * 8) || !f->d_off.ensure((n + 1) * 8) ||
+    if (!words.ensure(8)) return false;
+    if (!d_rule.ensure(n * 4) || !d_emit.ensure(n * 4) || !d_taglen.ensure(n * 4) || !f->d_len.ensure(n * 4) ||
+        !d_emit_idx.ensure((n + 1) * 8) || !d_tag_off.ensure((n + 1) * 8) || !f->d_off.ensure((n + 1) * 8) ||
         !f->d_scan_tmp.ensure(scan_tmp_elems(n) * sizeof(uint64_t)))
         return false;
-    if (m->tag_dirty) {
-        if (!m->d_tag.ensure(m->tag.size() + 16)) return false;
-        if (!m->tag.empty()) HIPOK(hipMemcpyAsync(m->d_tag.p, m->tag.data(), m->tag.size(), hipMemcpyHostToDevice, st));
+    if (tag_dirty) {
+        if (!d_tag.ensure(tag.size() + 16)) return false;
+        if (!tag.empty()) HIPOK(hipMemcpyAsync(d_tag.p, tag.data(), tag.size(), hipMemcpyHostToDevice, st));
         HIPOK(hipStreamSynchronize(st));
-        m->tag_dirty = false;
+        tag_dirty = false;
     }
-    Words *dw = m->d_words.as<Words>();
-    Words &hw = *m->hp_words.as<Words>();
-    Totals &tot = *(Totals *) (m->hp_words.as<uint8_t>() + sizeof(Words));
+    Words *dw = words.dev();
+    Words &hw = words.host();
+    Totals &tot = words.total();
     RtagArgs a;
     memset(&a, 0, sizeof(a));
     a.data = (const uint8_t *) in->data; a.row_off = in->row_off; a.n = n;
-    a.table = m->d_table.as<uint32_t>(); a.table_bytes = m->table_bytes; a.nrules = m->nrules;
-    a.rules = m->d_rules.as<GrepRule>(); a.caps = m->d_caps.as<RtagCap>();
-    a.tag = m->d_tag.as<uint8_t>(); a.tag_len = (uint32_t) m->tag.size();
-    a.rule = m->d_rule.as<uint32_t>(); a.keep_len = f->d_len.as<uint32_t>(); a.emit = m->d_emit.as<uint32_t>();
-    a.emit_idx = m->d_emit_idx.as<uint64_t>(); a.tag_lens = m->d_taglen.as<uint32_t>(); a.tag_off = m->d_tag_off.as<uint64_t>();
+    a.table = d_table.as<uint32_t>(); a.table_bytes = table_bytes; a.nrules = nrules;
+    a.rules = d_rules.as<GrepRule>(); a.caps = d_caps.as<RtagCap>();
+    a.tag = d_tag.as<uint8_t>(); a.tag_len = (uint32_t) tag.size();
+    a.rule = d_rule.as<uint32_t>(); a.keep_len = f->d_len.as<uint32_t>(); a.emit = d_emit.as<uint32_t>();
+    a.emit_idx = d_emit_idx.as<uint64_t>(); a.tag_lens = d_taglen.as<uint32_t>(); a.tag_off = d_tag_off.as<uint64_t>();
     a.first_bad = &dw->first_bad; a.counts = dw->counts;
     auto match_pass = [&](const char *name) {
-        memset(&hw, 0, sizeof(hw));
-        hw.first_bad = ~0ull;
-        HIPOK(hipMemcpyAsync(dw, &hw, sizeof(hw), hipMemcpyHostToDevice, st));
-        { ProfScope ps(f, st, name); launch_rtag_match(a, st); }
-        HIPOK(hipMemcpyAsync(&hw, dw, sizeof(hw), hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
-        return true;
+        return words.pass(f, st, name, [](Words &w) { memset(&w, 0, sizeof(w)); w.first_bad = ~0ull; }, [&] { launch_rtag_match(a, st); });
     };
     if (!match_pass("k_rtag_match")) return false;
     const unsigned long long fb = hw.first_bad;
@@ -405,83 +373,83 @@ bool run_rtag_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk
     f->last_out = hw.counts[0];
     if (hw.counts[3]) { set_err("filter_rewrite_tag: a record is larger than 4 GB"); return false; }
     if (hw.counts[2] == 0) return true;                                 // nothing matched: emitted_num == 0 (:517-522)
-    { ProfScope ps(f, st, "k_scan"); launch_scan(a.emit, nn, f->d_scan_tmp.as<uint64_t>(), m->d_emit_idx.as<uint64_t>(), st, nullptr); }
-    if (m->ncaps) launch_max_row_len(in->row_off, nn, &dw->max_row, st);
-    HIPOK(hipMemcpyAsync(&tot.n_emit, m->d_emit_idx.as<uint64_t>() + nn, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    { ProfScope ps(f, st, "k_scan"); launch_scan(a.emit, nn, f->d_scan_tmp.as<uint64_t>(), d_emit_idx.as<uint64_t>(), st, nullptr); }
+    if (ncaps) launch_max_row_len(in->row_off, nn, &dw->max_row, st);
+    HIPOK(hipMemcpyAsync(&tot.n_emit, d_emit_idx.as<uint64_t>() + nn, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIPOK(hipMemcpyAsync(&hw.max_row, &dw->max_row, sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
     const uint64_t n_emit = tot.n_emit;
     if (n_emit != hw.counts[2]) { set_err("filter_rewrite_tag: the emitted rows' scan disagrees with their count"); return false; }
     a.n_emit = n_emit;
     int waves = 65536 * (RT_BLOCK / 64);
-    if (m->ncaps) {
+    if (ncaps) {
         // the capture walk's scratch, per wave, as the parser's phase kernels size theirs (flbgpu.cpp run_generic): a state id every
         // CHK_STEP boundaries of the longest row; behind them the NFA engine's kept position sets where a rule's program runs on it
         uint32_t chk_len = (uint32_t) (hw.max_row / CHK_STEP) + 3;
         const uint32_t nfa_off = chk_len;
-        if (m->max_vw) chk_len = nfa_off + 2u * (uint32_t) (hw.max_row / rx::NFA_CHK + 2) * (m->max_vw + 1) + 2;
+        if (max_vw) chk_len = nfa_off + 2u * (uint32_t) (hw.max_row / rx::NFA_CHK + 2) * (max_vw + 1) + 2;
         const int cus = device_cus() > 0 ? device_cus() : 256;
         waves = cus * 8 * (RT_BLOCK / 64);
         while (waves > RT_BLOCK / 64 && (size_t) waves * 64 * chk_len * sizeof(uint16_t) > ((size_t) 1 << 30)) waves /= 2;
-        if (!m->d_chk.ensure((size_t) waves * 64 * chk_len * sizeof(uint16_t)) || !m->d_spans.ensure((size_t) RT_CAP_COLS * n_emit * 4 + 16)) return false;
-        a.chk = m->d_chk.as<uint16_t>(); a.chk_len = chk_len; a.chk_nfa_off = nfa_off; a.spans = m->d_spans.as<uint32_t>();
+        if (!d_chk.ensure((size_t) waves * 64 * chk_len * sizeof(uint16_t)) || !d_spans.ensure((size_t) RT_CAP_COLS * n_emit * 4 + 16)) return false;
+        a.chk = d_chk.as<uint16_t>(); a.chk_len = chk_len; a.chk_nfa_off = nfa_off; a.spans = d_spans.as<uint32_t>();
     }
     { ProfScope ps(f, st, "k_rtag(size)"); launch_rtag(a, false, waves, st); }
-    { ProfScope ps(f, st, "k_scan"); launch_scan(a.tag_lens, nn, f->d_scan_tmp.as<uint64_t>(), m->d_tag_off.as<uint64_t>(), st, nullptr); }
-    HIPOK(hipMemcpyAsync(&tot.tag_bytes, m->d_tag_off.as<uint64_t>() + nn, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    { ProfScope ps(f, st, "k_scan"); launch_scan(a.tag_lens, nn, f->d_scan_tmp.as<uint64_t>(), d_tag_off.as<uint64_t>(), st, nullptr); }
+    HIPOK(hipMemcpyAsync(&tot.tag_bytes, d_tag_off.as<uint64_t>() + nn, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIPOK(hipMemcpyAsync(&hw, dw, sizeof(hw), hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
     if (hw.counts[3]) { set_err("filter_rewrite_tag: a tag is larger than 4 GB"); return false; }
-    if (!m->d_tags.ensure(tot.tag_bytes + 16) || !m->d_table_out.ensure(n_emit * sizeof(RtagEmitted) + 16)) return false;
-    a.tags = m->d_tags.as<uint8_t>(); a.table_out = m->d_table_out.as<RtagEmitted>();
+    if (!d_tags.ensure(tot.tag_bytes + 16) || !d_table_out.ensure(n_emit * sizeof(RtagEmitted) + 16)) return false;
+    a.tags = d_tags.as<uint8_t>(); a.table_out = d_table_out.as<RtagEmitted>();
     { ProfScope ps(f, st, "k_rtag(emit)"); launch_rtag(a, true, waves, st); }
     HIPOK(hipMemcpyAsync(&hw, dw, sizeof(hw), hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
     if (hw.counts[4] || hw.counts[3]) {
-        m->mismatch += hw.counts[4];
+        mismatch += hw.counts[4];
         set_err("filter_rewrite_tag: %llu rows were written with another tag length than they were sized with (or their capture walk failed)", hw.counts[4]);
         return false;
     }
-    m->last_n = n_emit; m->last_tag_bytes = tot.tag_bytes; m->on_host = false;
+    last_n = n_emit; last_tag_bytes = tot.tag_bytes; on_host = false;
     uint64_t accepted = n_emit, n_ref = 0;
     if (f->rtag_host_call) {
         // the emitter's side: in_emitter_add_record per emission, in record order, on the caller's bytes
-        m->h_recs.resize(n_emit);
-        m->h_tags.resize(tot.tag_bytes);
-        HIPOK(hipMemcpy(m->h_recs.data(), m->d_table_out.p, n_emit * sizeof(RtagEmitted), hipMemcpyDeviceToHost));
-        if (tot.tag_bytes) HIPOK(hipMemcpy(m->h_tags.data(), m->d_tags.p, tot.tag_bytes, hipMemcpyDeviceToHost));
-        if (in->data == f->rtag_dev_base && f->rtag_host_base) m->input = f->rtag_host_base;
+        h_recs.resize(n_emit);
+        h_tags.resize(tot.tag_bytes);
+        HIPOK(hipMemcpy(h_recs.data(), d_table_out.p, n_emit * sizeof(RtagEmitted), hipMemcpyDeviceToHost));
+        if (tot.tag_bytes) HIPOK(hipMemcpy(h_tags.data(), d_tags.p, tot.tag_bytes, hipMemcpyDeviceToHost));
+        if (in->data == f->rtag_dev_base && f->rtag_host_base) input = f->rtag_host_base;
         else {
             // behind another filter of a chain: that filter's output is this one's input, and it lives on the device
-            m->h_input.resize(in->bytes);
-            if (in->bytes) HIPOK(hipMemcpy(m->h_input.data(), in->data, in->bytes, hipMemcpyDeviceToHost));
-            m->input = m->h_input.data();
+            h_input.resize(in->bytes);
+            if (in->bytes) HIPOK(hipMemcpy(h_input.data(), in->data, in->bytes, hipMemcpyDeviceToHost));
+            input = h_input.data();
         }
-        m->input_bytes = in->bytes;
-        m->on_host = true;
-        if (m->emit_cb) {
+        input_bytes = in->bytes;
+        on_host = true;
+        if (emit_cb) {
             std::vector<uint32_t> bits((n_emit + 31) / 32, 0u);
             size_t w = 0;
             for (uint64_t e = 0; e < n_emit; e++) {
-                const RtagEmitted &r = m->h_recs[e];
-                const int rc = m->emit_cb(m->emit_ctx, (const char *) m->h_tags.data() + r.tag_off, (int) r.tag_len, m->input + r.in_off, r.len);
+                const RtagEmitted &r = h_recs[e];
+                const int rc = emit_cb(emit_ctx, (const char *) h_tags.data() + r.tag_off, (int) r.tag_len, input + r.in_off, r.len);
                 if (rc < 0) { bits[e >> 5] |= 1u << (e & 31); n_ref++; }
-                else m->h_recs[w++] = r;
+                else h_recs[w++] = r;
             }
-            m->h_recs.resize(w);
+            h_recs.resize(w);
             accepted = n_emit - n_ref;
             if (n_ref) {
-                if (!m->d_refused.ensure(bits.size() * 4)) return false;
-                HIPOK(hipMemcpyAsync(m->d_refused.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, st));
-                launch_rtag_refuse(a, m->d_refused.as<uint32_t>(), st);
+                if (!d_refused.ensure(bits.size() * 4)) return false;
+                HIPOK(hipMemcpyAsync(d_refused.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice, st));
+                launch_rtag_refuse(a, d_refused.as<uint32_t>(), st);
                 HIPOK(hipStreamSynchronize(st));
             }
         }
     }
-    m->emitted += accepted; m->refused += n_ref; m->tag_bytes += hw.counts[5];
+    emitted += accepted; refused += n_ref; tag_bytes += hw.counts[5];
     if (accepted == 0) return true;                                     // emitted_num == 0 (:517-522)
     if (fb != ~0ull || garbage) return true;                            // "Log event encoder error" (:546-551)
-    unsigned long long *d_kept = (unsigned long long *) (m->d_words.as<uint8_t>() + sizeof(Words));
+    unsigned long long *d_kept = (unsigned long long *) (dw + 1);
     HIPOK(hipMemsetAsync(d_kept, 0, sizeof(unsigned long long), st));
     { ProfScope ps(f, st, "k_scan"); launch_scan(a.keep_len, n, f->d_scan_tmp.as<uint64_t>(), f->d_off.as<uint64_t>(), st, d_kept); }
     HIPOK(hipMemcpyAsync(&tot.kept_bytes, f->d_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
@@ -493,7 +461,7 @@ bool run_rtag_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk
     ta.out_off = f->d_off.as<uint64_t>(); ta.out = f->d_out.as<uint8_t>(); ta.out_cap = 0;
     if (tot.kept_bytes) { ProfScope ps(f, st, "k_gather"); launch_gather(ta, st); }
     HIPOK(hipStreamSynchronize(st));
-    out->data = f->d_out.p; out->row_off = f->d_off.as<uint64_t>(); out->n = n; out->bytes = tot.kept_bytes;
+    set_out(f, out, n, tot.kept_bytes);
     f->last_out = tot.kept;
     *ret = FLBGPU_FILTER_MODIFIED;
     return true;

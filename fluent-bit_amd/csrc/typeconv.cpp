@@ -1,7 +1,7 @@
 // typeconv.cpp -- filter_type_converter (plugins/filter_type_converter/type_converter.c): the configuration as configure() reads it
 // (:108-140, config_rule :57-106, behind the config map of :366-388), the device program behind it, and one
 // cb_type_converter_filter call on a device chunk (:182-353).  The per-record work is typeconv_kernels.inc.
-#include "host_int.hpp"
+#include "filter_host.hpp"
 #include "typeconv.hpp"
 
 using namespace flbgpu;
@@ -15,13 +15,6 @@ struct TRule {
     std::string from, to_key;
 };
 struct TProgram { std::vector<TRule> rules; };
-
-std::string hexs(const std::string &s) {
-    static const char *hx = "0123456789abcdef";
-    std::string o;
-    for (unsigned char c : s) { o.push_back(hx[c >> 4]); o.push_back(hx[c & 15]); }
-    return o;
-}
 
 // flb_typecast_str_to_type_t (src/flb_typecast.c:27-49): strncasecmp(word, name, strlen(word)) in this order -- the word is a
 // prefix of the name, the empty word of the first one
@@ -239,89 +232,70 @@ int flbgpu::ra_split(const std::string &a, std::vector<RaPart> &parts, std::stri
     return RA_SPLIT_OK;
 }
 
-struct TypeconvState {
+namespace {
+
+bool front(int nprops, const char *const *names, const char *const *values, TProgram &pg) {
+    return parse_front("type_converter", nprops, names, values, [&](std::string &why) { return parse_program(nprops, names, values, pg, why); });
+}
+
+struct TypeconvState : FilterState {
+    struct Words { unsigned long long first_bad, counts[7]; };
     int nrules = 0;
     uint32_t table_bytes = 0;
     uint64_t done = 0, failed = 0, undefined = 0, mismatch = 0;        // since the filter was created (flbgpu_type_converter_counters)
-    DevBuf d_table, d_words;
-    PinnedBuf hp_words;
+    ScopedDevBuf d_table;
+    CallWords<Words> words;
+    bool run(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) override;
 };
 
-void typeconv_state_destroy(TypeconvState *m) {
-    if (!m) return;
-    m->d_table.release(); m->d_words.release();
-    m->hp_words.release();
-    delete m;
-}
+}  // namespace
 
 extern "C" int flbgpu_type_converter_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap) {
     TProgram pg;
-    std::string why;
-    if (nprops < 0 || (nprops > 0 && (!names || !values))) { set_err("filter_type_converter: bad arguments"); return -1; }
-    if (!parse_program(nprops, names, values, pg, why)) { set_err("filter_type_converter: %s", why.c_str()); return -1; }
-    const std::string d = describe(pg);
-    if (desc && cap) { const size_t n = d.size() < cap - 1 ? d.size() : cap - 1; memcpy(desc, d.data(), n); desc[n] = 0; }
+    if (!front(nprops, names, values, pg)) return -1;
+    put_desc(desc, cap, describe(pg));
     return 0;
 }
 
 extern "C" flbgpu_filter *flbgpu_filter_type_converter_create(int nprops, const char *const *names, const char *const *values) {
     TProgram pg;
-    std::string why;
-    if (nprops < 0 || (nprops > 0 && (!names || !values))) { set_err("filter_type_converter: bad arguments"); return nullptr; }
-    if (!parse_program(nprops, names, values, pg, why)) { set_err("filter_type_converter: %s", why.c_str()); return nullptr; }
+    if (!front(nprops, names, values, pg)) return nullptr;
     auto *f = new flbgpu_filter();
     f->kind = F_TYPECONV;
     auto *m = new TypeconvState();
-    f->typeconv = m;
+    f->state = m;
     m->nrules = (int) pg.rules.size();
     std::vector<uint32_t> table;
     build_table(pg, table);
     m->table_bytes = (uint32_t) (table.size() * 4);
-    if (!filter_common_init(f) || !m->d_table.ensure(m->table_bytes + 16) ||
-        hipMemcpy(m->d_table.p, table.data(), m->table_bytes, hipMemcpyHostToDevice) != hipSuccess) {
-        delete f;
-        return nullptr;
-    }
+    if (!filter_common_init(f) || !upload(m->d_table, table)) { delete f; return nullptr; }
     return f;
 }
 
 extern "C" void flbgpu_type_converter_counters(flbgpu_filter *f, uint64_t out[4]) {
     out[0] = out[1] = out[2] = out[3] = 0;
-    if (!f || f->kind != F_TYPECONV || !f->typeconv) return;
-    out[0] = f->typeconv->done; out[1] = f->typeconv->failed; out[2] = f->typeconv->undefined; out[3] = f->typeconv->mismatch;
+    if (auto *m = state_of<TypeconvState>(f, F_TYPECONV)) { out[0] = m->done; out[1] = m->failed; out[2] = m->undefined; out[3] = m->mismatch; }
 }
 
 // cb_type_converter_filter (:182-353) on a device chunk.  Every decoded record goes into the encoder, but the call hands the buffer
 // on only when a conversion succeeded somewhere (:321-326) AND the decoder's loop ended on a clean end of data (:328-346): a record
 // the decoder refuses, or undecodable bytes behind the rows (`garbage`), make the call answer NOTOUCH whatever was converted in front.
-bool run_typeconv_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) {
-    TypeconvState *m = f->typeconv;
+bool TypeconvState::run(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret, bool garbage) {
     const uint64_t n = in->n;
     *ret = FLBGPU_FILTER_NOTOUCH;
     f->last_in = 0; f->last_out = 0;
     if (n == 0) return true;
-    struct Words { unsigned long long first_bad, counts[7]; };
-    if (!m->d_words.ensure(sizeof(Words)) || !m->hp_words.ensure(sizeof(Words) + sizeof(uint64_t))) return false;
-    if (!f->d_len.ensure(n * sizeof(uint32_t)) || !f->d_off.ensure((n + 1) * sizeof(uint64_t)) ||
-        !f->d_scan_tmp.ensure(scan_tmp_elems(n) * sizeof(uint64_t)))
-        return false;
-    Words *dw = m->d_words.as<Words>();
-    Words &hw = *m->hp_words.as<Words>();
-    uint64_t &total = *(uint64_t *) (m->hp_words.as<uint8_t>() + sizeof(Words));
+    if (!words.ensure() || !ensure_row_columns(f, n)) return false;
+    Words *dw = words.dev();
+    Words &hw = words.host();
     TypeconvArgs a;
     memset(&a, 0, sizeof(a));
     a.data = (const uint8_t *) in->data; a.row_off = in->row_off; a.n = n;
-    a.table = m->d_table.as<uint32_t>(); a.table_bytes = m->table_bytes; a.nrules = m->nrules;
+    a.table = d_table.as<uint32_t>(); a.table_bytes = table_bytes; a.nrules = nrules;
     a.len = f->d_len.as<uint32_t>();
     a.first_bad = &dw->first_bad; a.counts = dw->counts;
     auto size_pass = [&](const char *name) {
-        memset(&hw, 0, sizeof(hw));
-        hw.first_bad = ~0ull;
-        HIPOK(hipMemcpyAsync(dw, &hw, sizeof(hw), hipMemcpyHostToDevice, st));
-        { ProfScope ps(f, st, name); launch_typeconv(a, false, st); }
-        HIPOK(hipMemcpyAsync(&hw, dw, sizeof(hw), hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
-        return true;
+        return words.pass(f, st, name, [](Words &w) { memset(&w, 0, sizeof(w)); w.first_bad = ~0ull; }, [&] { launch_typeconv(a, false, st); });
     };
     if (!size_pass("k_typeconv(size)")) return false;
     const unsigned long long fb = hw.first_bad;
@@ -331,23 +305,20 @@ bool run_typeconv_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_c
         a.n = fb;
         if (!size_pass("k_typeconv(size, in front of a decoder error)")) return false;
     }
-    m->done += hw.counts[2]; m->failed += hw.counts[3]; m->undefined += hw.counts[4];
+    done += hw.counts[2]; failed += hw.counts[3]; undefined += hw.counts[4];
     f->last_in = hw.counts[0];
     f->last_out = hw.counts[0];
     if (fb != ~0ull || garbage) return true;                            // "Log event encoder error" (:341-346)
     if (hw.counts[5]) { set_err("filter_type_converter: a record's output is larger than 4 GB"); return false; }
     if (hw.counts[2] == 0 || hw.counts[1] == 0) return true;            // is_record_modified stayed false (:321-326)
-    { ProfScope ps(f, st, "k_scan"); launch_scan(a.len, n, f->d_scan_tmp.as<uint64_t>(), f->d_off.as<uint64_t>(), st, nullptr); }
-    HIPOK(hipMemcpyAsync(&total, f->d_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
-    if (!f->d_out.ensure(total + 16)) return false;
+    if (!scan_lengths(f, st, a.len, n, &words.total())) return false;
     a.out_off = f->d_off.as<uint64_t>(); a.out = f->d_out.as<uint8_t>();
     { ProfScope ps(f, st, "k_typeconv(emit)"); launch_typeconv(a, true, st); }
     HIPOK(hipMemcpyAsync(&hw.counts[6], &dw->counts[6], sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
-    m->mismatch += hw.counts[6];
+    mismatch += hw.counts[6];
     if (hw.counts[6]) { set_err("filter_type_converter: %llu rows were emitted with another length than they were sized", hw.counts[6]); return false; }
-    out->data = f->d_out.p; out->row_off = f->d_off.as<uint64_t>(); out->n = n; out->bytes = total;
+    set_out(f, out, n, words.total());
     f->last_out = hw.counts[1];
     *ret = FLBGPU_FILTER_MODIFIED;
     return true;

@@ -2,11 +2,11 @@
 // UndefinedBehaviorSanitizer: flbgpu_checklist_parse_check (csrc/checklist.cpp: the front end and the list loader) over every
 // recorded configuration with its list file (tests/golden/checklist_ref_cases.json, read with the few lines of JSON below) and over
 // list files at the loader's edges -- lines of 2044 to 2047 bytes, a last line without a newline, NUL bytes anywhere.  It needs no
-// device.  checklist.cpp is compiled into the program with the sanitizers; what it calls outside itself (the record accessor's
-// parser, the token splitter) comes from the ordinary libflbgpu.so:
+// device.  checklist.cpp and the filters' shared front (filter_host.cpp) are compiled into the program with the sanitizers; what they
+// call outside themselves (the record accessor's parser, the token splitter) comes from the ordinary libflbgpu.so:
 //
 //   hipcc --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer -O1 -g -std=c++17 \
-//       -o checklist_sanitize tools/checklist_sanitize.cpp fluent-bit_amd/csrc/checklist.cpp \
+//       -o checklist_sanitize tools/checklist_sanitize.cpp fluent-bit_amd/csrc/checklist.cpp fluent-bit_amd/csrc/filter_host.cpp \
 //       -Lfluent-bit_amd/csrc -lflbgpu -Wl,-rpath,$PWD/fluent-bit_amd/csrc
 //   ./checklist_sanitize tests/golden/checklist_ref_cases.json
 //

@@ -4,13 +4,14 @@
 //     configurations -- property names without case, lists of parser names with blanks and empty entries, long names, missing
 //     handles.  Without a device create refuses every configuration that reaches the parser (the built-ins' tables live on the device):
 //     every object built on the way is freed again.
-//   * the host side of a call's bookkeeping, which run_mlfilter_dev keeps in functions free of device calls (csrc/mlfilter.hpp), driven
+//   * the host side of a call's bookkeeping, which MlFilterState::run keeps in functions free of device calls (csrc/mlfilter.hpp), driven
 //     with made-up device words: the rows in front of a decoder error, the truncation rounds up to their limit, what the words of a call
 //     mean (go on / hand back and count / fail), and the stream and the totals moving on success only.
-// mlfilter.cpp is compiled into the program with the sanitizers; what it calls outside itself comes from the ordinary libflbgpu.so:
+// mlfilter.cpp and the filters' shared front (filter_host.cpp) are compiled into the program with the sanitizers; what they call
+// outside themselves comes from the ordinary libflbgpu.so:
 //
 //   hipcc --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer -O1 -g -std=c++17 \
-//       -o multiline_filter_sanitize tools/multiline_filter_sanitize.cpp fluent-bit_amd/csrc/mlfilter.cpp \
+//       -o multiline_filter_sanitize tools/multiline_filter_sanitize.cpp fluent-bit_amd/csrc/mlfilter.cpp fluent-bit_amd/csrc/filter_host.cpp \
 //       -Lfluent-bit_amd/csrc -lflbgpu -Wl,-rpath,$PWD/fluent-bit_amd/csrc
 //   ./multiline_filter_sanitize
 //

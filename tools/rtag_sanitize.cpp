@@ -1,13 +1,13 @@
 // rtag_sanitize.cpp -- a stand-alone driver for the host code of filter_rewrite_tag under AddressSanitizer and
 // UndefinedBehaviorSanitizer: flbgpu_rewrite_tag_parse_check (csrc/rtag.cpp) over the front-end cases, the accessor splitter that moved
 // out of typeconv.cpp's private part (ra_split, reached through both filters' parse checks) and the two number formats a tag is
-// composed with, "%ld" and "%f" (csrc/numconv_host.cpp), over the number edges.  It needs no device.  rtag.cpp, typeconv.cpp and
-// numconv_host.cpp are compiled into the program with the sanitizers; what they call outside themselves (the regex compiler, the
+// composed with, "%ld" and "%f" (csrc/numconv_host.cpp), over the number edges.  It needs no device.  rtag.cpp, typeconv.cpp, the filters'
+// shared front (filter_host.cpp) and numconv_host.cpp are compiled into the program with the sanitizers; what they call outside themselves (the regex compiler, the
 // record accessor's parser, the token splitter) comes from the ordinary libflbgpu.so:
 //
 //   hipcc --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer -O1 -g -std=c++17 \
 //       -o rtag_sanitize tools/rtag_sanitize.cpp fluent-bit_amd/csrc/rtag.cpp fluent-bit_amd/csrc/typeconv.cpp \
-//       fluent-bit_amd/csrc/numconv_host.cpp -Lfluent-bit_amd/csrc -lflbgpu -Wl,-rpath,$PWD/fluent-bit_amd/csrc
+//       fluent-bit_amd/csrc/filter_host.cpp fluent-bit_amd/csrc/numconv_host.cpp -Lfluent-bit_amd/csrc -lflbgpu -Wl,-rpath,$PWD/fluent-bit_amd/csrc
 //   ./rtag_sanitize
 //
 // It prints how many configurations were accepted and refused and how many numbers went through, and ends with "clean" and status 0;

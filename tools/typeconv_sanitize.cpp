@@ -1,12 +1,12 @@
 // typeconv_sanitize.cpp -- a stand-alone driver for the host code of filter_type_converter under AddressSanitizer and
 // UndefinedBehaviorSanitizer: flbgpu_type_converter_parse_check (csrc/typeconv.cpp) over the front-end cases and the flbgpu_nc_*
-// functions filter_type_converter added (csrc/numconv_host.cpp) over the number edges.  It needs no device.  typeconv.cpp and
-// numconv_host.cpp are compiled into the program with the sanitizers; what they call outside themselves (the record accessor's
+// functions filter_type_converter added (csrc/numconv_host.cpp) over the number edges.  It needs no device.  typeconv.cpp, the
+// filters' shared front (filter_host.cpp) and numconv_host.cpp are compiled into the program with the sanitizers; what they call outside themselves (the record accessor's
 // parser, the token splitter) comes from the ordinary libflbgpu.so:
 //
 //   hipcc --offload-arch=gfx950 -Xarch_host -fsanitize=address,undefined -fno-omit-frame-pointer -O1 -g -std=c++17 \
-//       -o typeconv_sanitize tools/typeconv_sanitize.cpp fluent-bit_amd/csrc/typeconv.cpp fluent-bit_amd/csrc/numconv_host.cpp \
-//       -Lfluent-bit_amd/csrc -lflbgpu -Wl,-rpath,$PWD/fluent-bit_amd/csrc
+//       -o typeconv_sanitize tools/typeconv_sanitize.cpp fluent-bit_amd/csrc/typeconv.cpp fluent-bit_amd/csrc/filter_host.cpp \
+//       fluent-bit_amd/csrc/numconv_host.cpp -Lfluent-bit_amd/csrc -lflbgpu -Wl,-rpath,$PWD/fluent-bit_amd/csrc
 //   ./typeconv_sanitize
 //
 // It prints how many programs were accepted and refused and how many numbers went through, and ends with "clean" and status 0; a
