@@ -86,6 +86,16 @@ def lib():
     L.flbgpu_checklist_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
     L.flbgpu_checklist_counters.restype = None
     L.flbgpu_checklist_counters.argtypes = [c_void_p, POINTER(c_uint64)]
+    L.flbgpu_filter_expect_create.restype = c_void_p
+    L.flbgpu_filter_expect_create.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p)]
+    L.flbgpu_expect_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
+    L.flbgpu_expect_counters.restype = None
+    L.flbgpu_expect_counters.argtypes = [c_void_p, POINTER(c_uint64)]
+    L.flbgpu_expect_failures.argtypes = [c_void_p, c_void_p]
+    L.flbgpu_expect_failures_dev.argtypes = [c_void_p, c_void_p]
+    L.flbgpu_expect_failure_text.argtypes = [c_void_p, c_uint64, c_char_p, c_size_t]
+    L.flbgpu_expect_text_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_char_p, c_size_t,
+                                           c_char_p, c_size_t]
     L.flbgpu_filter_rewrite_tag_create.restype = c_void_p
     L.flbgpu_filter_rewrite_tag_create.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p)]
     L.flbgpu_rewrite_tag_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
@@ -441,6 +451,73 @@ class FilterChecklist(_PropsFilter):
 def checklist_parse_check(props):
     """the configuration and the loaded list as one line of text (host only); raises ValueError where create refuses"""
     return _parse_check("flbgpu_checklist_parse_check", props, 1 << 17)
+
+
+class ExpectFailure(ctypes.Structure):
+    _fields_ = [("in_off", c_uint64), ("val_off", c_uint64), ("len", ctypes.c_uint32), ("val_len", ctypes.c_uint32), ("rule", ctypes.c_uint32),
+                ("kind", ctypes.c_uint32), ("vtype", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class ExpectFailures(ctypes.Structure):
+    _fields_ = [("count", c_uint64), ("recs", c_void_p), ("input", c_void_p), ("input_bytes", c_uint64)]
+
+
+class FilterExpect(_PropsFilter):
+    """filter_expect: props = [(name, value), ...] in configuration order, e.g. [("key_exists", "$log"), ("key_val_eq", "$level info"),
+    ("action", "result_key")] (plugins/filter_expect/expect.c).  warn and exit answer NOTOUCH; what failed is in failures()"""
+    _CREATE = "flbgpu_filter_expect_create"
+    _COUNTERS = "flbgpu_expect_counters"
+
+    def counters(self):
+        """(records checked, records failed, exit requests, size/emit mismatches) since the filter was created
+        (flb_gpu.h flbgpu_expect_counters)"""
+        return self._counters()
+
+    def failures(self):
+        """the last call's failures in record order: [(in_off, len, rule number, failure kind, value type, val_off, val_len), ...];
+        the offsets index the chunk that call was given"""
+        e = ExpectFailures()
+        if lib().flbgpu_expect_failures(self.h, byref(e)) != 0:
+            raise RuntimeError(last_error())
+        recs = ctypes.cast(e.recs, POINTER(ExpectFailure))
+        return [(int(r.in_off), int(r.len), int(r.rule), int(r.kind), int(r.vtype), int(r.val_off), int(r.val_len)) for r in (recs[i] for i in range(e.count))]
+
+    def failures_input(self):
+        """after a host-level call that had failures: the bytes their offsets index (the caller's buffer, or this filter's input behind
+        another filter of a chain); None after a device-level call"""
+        e = ExpectFailures()
+        if lib().flbgpu_expect_failures(self.h, byref(e)) != 0:
+            raise RuntimeError(last_error())
+        return ctypes.string_at(e.input, e.input_bytes) if e.input else None
+
+    def failures_dev(self):
+        """after filter_dev: (count, device pointer of the table)"""
+        e = ExpectFailures()
+        if lib().flbgpu_expect_failures_dev(self.h, byref(e)) != 0:
+            raise RuntimeError(last_error())
+        return int(e.count), e.recs
+
+    def failure_text(self, i):
+        """the reference's message for failure i of the last call, up to and including "Record content:\\n" (bytes)"""
+        buf = ctypes.create_string_buffer(1 << 17)
+        n = lib().flbgpu_expect_failure_text(self.h, i, buf, len(buf))
+        if n < 0:
+            raise RuntimeError(last_error())
+        return buf.value
+
+
+def expect_parse_check(props):
+    """the action, the result key and the numbered rules as one line of text (host only); raises ValueError where create refuses"""
+    return _parse_check("flbgpu_expect_parse_check", props, 1 << 17)
+
+
+def expect_text_check(props, rule, kind, vtype, value=b""):
+    """the reference's message for a failure given by hand (host only, bytes); raises ValueError where the library refuses"""
+    buf = ctypes.create_string_buffer(1 << 17)
+    value = bytes(value)
+    if lib().flbgpu_expect_text_check(*_props(props), rule, kind, vtype, value, len(value), buf, len(buf)) < 0:
+        raise ValueError(last_error())
+    return buf.value
 
 
 class RtagEmittedRec(ctypes.Structure):

@@ -2377,7 +2377,7 @@ static int run_any_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_
         ok = run_l2m_dev(f, in, st, &ret);
         if (ok && ret == FLBGPU_FILTER_MODIFIED && out) memset(out, 0, sizeof(*out));   // discard_logs: every record dropped
     }
-    else if (f->kind >= F_MODIFY && f->kind <= F_CHECKLIST) ok = f->state->run(f, in, out, st, &ret, garbage);
+    else if (f->kind >= F_MODIFY && f->kind <= F_EXPECT) ok = f->state->run(f, in, out, st, &ret, garbage);
     else ok = f->kind == F_PARSER ? run_parser_dev(f, in, out, st, &ret) : run_grep_dev(f, in, out, st, &ret, garbage);
     if (!ok) return FLBGPU_FILTER_NOTOUCH;      // errors degrade to NOTOUCH (SURVEY 8b "Errors")
     return ret;
@@ -2921,9 +2921,9 @@ extern "C" int flbgpu_filter_chain_run(flbgpu_filter *const *filters, int nfilte
     struct RtagScope {
         flbgpu_filter *const *fl; int n;
         RtagScope(flbgpu_filter *const *fl_, int n_, const void *dev, const void *host) : fl(fl_), n(n_) {
-            for (int i = 0; i < n; i++) if (fl[i]->kind == F_RTAG) { fl[i]->rtag_host_call = true; fl[i]->rtag_dev_base = dev; fl[i]->rtag_host_base = (const uint8_t *) host; }
+            for (int i = 0; i < n; i++) if (fl[i]->kind == F_RTAG || fl[i]->kind == F_EXPECT) { fl[i]->rtag_host_call = true; fl[i]->rtag_dev_base = dev; fl[i]->rtag_host_base = (const uint8_t *) host; }
         }
-        ~RtagScope() { for (int i = 0; i < n; i++) if (fl[i]->kind == F_RTAG) { fl[i]->rtag_host_call = false; fl[i]->rtag_dev_base = nullptr; fl[i]->rtag_host_base = nullptr; } }
+        ~RtagScope() { for (int i = 0; i < n; i++) if (fl[i]->kind == F_RTAG || fl[i]->kind == F_EXPECT) { fl[i]->rtag_host_call = false; fl[i]->rtag_dev_base = nullptr; fl[i]->rtag_host_base = nullptr; } }
     } rtag_scope(filters, nfilters, f->h_in_data.p, data);
     {
         PhaseScope ph(HP_CHAIN);

@@ -288,6 +288,69 @@ int flbgpu_checklist_parse_check(int nprops, const char *const *names, const cha
  * row's room, and a call that counts one answers NOTOUCH) */
 void flbgpu_checklist_counters(flbgpu_filter *f, uint64_t out[4]);
 
+/* ---- filter_expect: replaces cb_expect_init / cb_expect_filter / cb_expect_exit ----
+ * plugins/filter_expect/expect.c:146-230 (context_create, behind the config map of :580-632), 275-396 (rule_apply), 398-564 (one
+ * call); src/flb_record_accessor.c:767-814 and src/flb_ra_key.c:31-271 (the value a rule looks at).
+ * (names[i], values[i]) are the instance's properties in configuration order, names without case:
+ *   key_exists, key_not_exists, key_val_is_null, key_val_is_not_null      a record accessor: a plain name, `$name`,
+ *                  `$name['a']['b']`, `$name['a'][1]` (a path may end on an index).  An accessor whose first part is no key (`$TAG`,
+ *                  `$0`, an empty text) never finds anything.  The value is a STR, BIN, MAP, bool, number or nil; an ARRAY or EXT
+ *                  value is not found.  Duplicate keys: the last one wins.
+ *   key_val_eq     "ACCESSOR TEXT", split as flb_slist_split_string(.., ' ', 1) splits: the first word, then the rest of the line as
+ *                  it is ("k a b  c" expects "a b  c"; a single word is accessor and expected text at once).  Fails when the value
+ *                  is not found, or is a STR of another length or other bytes; a value of any other type passes.
+ *   action         warn (default), exit or result_key, without case; set once.  It takes a rule number like a rule does.
+ *   result_key     default "matched"; set once; takes no rule number.
+ * The rules run in configuration order and the first one that fails ends the record.  warn and exit answer NOTOUCH and hand the
+ * chunk on; exit stops at the first failing record and counts an exit request (the shim's flb_engine_exit_status(config, 255)).
+ * result_key rebuilds every record as 92 92 d7 00 <sec> <nsec>, the metadata re-packed, a map32 header, {result_key: true|false},
+ * then the body's own entries re-packed (an entry with the same key stays); group markers go out as they are, a record whose time
+ * the EventTime cannot hold is dropped, and the call answers MODIFIED unless the decoder's loop ended on an error.  create answers
+ * NULL + last_error where the reference refuses or dies (a property set twice, an unknown property or action, an accessor the
+ * grammar refuses, a key_val_eq without a value) and at this library's limits: `${` in a value, more than 64 rules, a rule table over
+ * 32768 bytes, a result_key over 65535 bytes.  Runs through flbgpu_filter_run[_dev], flbgpu_filter_chain_run[_dev],
+ * flbgpu_filter_last_counts (records checked / records emitted) and flbgpu_filter_destroy. */
+flbgpu_filter *flbgpu_filter_expect_create(int nprops, const char *const *names, const char *const *values);
+/* host only, no device: the configuration as one line of text --
+ * "action=<warn|exit|result_key>;result_key=<hex>;#<rule number>:<rule name>:<K<hex name>{.<hex sub-key>|[<index>]}...|->[:E<hex
+ * expected text>];..." (an `action` property appears as a rule named action) -- 0, or -1 + last_error where create refuses */
+int flbgpu_expect_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap);
+/* since the filter was created: out[0] records checked, out[1] records failed, out[2] exit requests, out[3] rows whose emitted
+ * length differed from their sized length (always 0; the emit pass never stores outside a row's room, and a call that counts one
+ * answers NOTOUCH) */
+void flbgpu_expect_counters(flbgpu_filter *f, uint64_t out[4]);
+/* the last call's failures, in record order (under exit: the first one only): recs[i] = the record at bytes [in_off, in_off + len)
+ * of the instance's input chunk, the number of the rule that failed, how (1 not found, 2 exists, 3 a value of the wrong type, 4 a
+ * STR that differs), the value's type (0 none, 1 boolean -- a MAP too --, 2 integer, 3 float, 4 string, 5 null, 6 binary) and, for a
+ * STR, its payload at [val_off, val_off + val_len).  flbgpu_expect_failures answers host pointers; input is the caller's buffer after
+ * a host-level call (a filter-owned copy behind another filter of a chain) and NULL after a device-level one.  The _dev twin answers
+ * recs as a device pointer after flbgpu_filter_run_dev (input stays NULL: the offsets index the chunk the caller passed).  The
+ * storage is filter-owned and valid until the next call on this filter or its destruction.  0, or -1 + last_error. */
+typedef struct flbgpu_expect_failure {
+    uint64_t in_off, val_off;
+    uint32_t len, val_len;
+    uint32_t rule, kind, vtype, reserved;
+} flbgpu_expect_failure;
+typedef struct flbgpu_expect_failures_t {
+    uint64_t count;
+    const flbgpu_expect_failure *recs;
+    const uint8_t *input;
+    uint64_t input_bytes;
+} flbgpu_expect_failures_t;
+int flbgpu_expect_failures(flbgpu_filter *f, flbgpu_expect_failures_t *out);
+int flbgpu_expect_failures_dev(flbgpu_filter *f, flbgpu_expect_failures_t *out);
+/* host only (no kernel runs): the message the reference logs for failure i of the last call, in its own wording -- "exception on
+ * rule #n '<rule>', key '<value>' not found." and its kin, key_val_eq's not-found text naming 'key_val_is_null' as the reference
+ * does -- up to and including " Record content:\n"; the record's JSON behind it is the caller's (flb_msgpack_to_json_str over the
+ * table's span).  A STR value is read from the input chunk, which has to be alive still.  Cut to cap - 1 bytes and terminated;
+ * answers the uncut length, or -1 + last_error. */
+int flbgpu_expect_failure_text(flbgpu_filter *f, uint64_t i, char *buf, size_t cap);
+/* host only, no device and no filter: the same message for a failure given by hand -- the properties, the rule's number, how it
+ * failed, the value's type and, for a STR that differs, its bytes.  0 or more: the uncut length; -1 + last_error where create
+ * refuses the properties or the number names no rule that can fail. */
+int flbgpu_expect_text_check(int nprops, const char *const *names, const char *const *values, uint64_t rule, uint32_t kind, uint32_t vtype,
+                             const void *val, size_t val_len, char *buf, size_t cap);
+
 /* ---- filter_rewrite_tag: replaces cb_rewrite_tag_init / cb_rewrite_tag_filter / cb_rewrite_tag_exit ----
  * plugins/filter_rewrite_tag/rewrite_tag.c:112-190 (process_config, behind the config map of :590-613), 356-423 (process_record),
  * 425-557 (one call); src/flb_record_accessor.c:74-230 (the parts of an accessor), 456-619 (ra_translate_*), 644-699
