@@ -36,6 +36,9 @@ def test_random_corpus_against_oracle(g):
 
 
 def test_large_chunks_and_object_reuse(g):
+    """the first loop's chunks end at their first truncated or garbage row: the oracle prints 5 .. 136 of their 2000 rows (three waves at
+    most); the second loop's chunks are clean, and every one of their 2000 records prints"""
+    from synth import mp, ext_ts, KV
     r = random.Random(9)
     for fmt in ("json", "stream", "lines"):
         for df in ("double", "iso8601", "epoch", "java_sql_timestamp", "epoch_ms"):
@@ -46,6 +49,16 @@ def test_large_chunks_and_object_reuse(g):
                 cfg = dict(json_format=g.JSON_FORMAT[fmt], date_format=g.JSON_DATE[df], date_key=b"date")
                 want = ob.msgpack_to_json_format(chunk, cfg["json_format"], cfg["date_format"], b"date", esc, 0)
                 assert f.format(chunk) == want
+            # 2 000 valid records with random metadata, 600 of them inside one group
+            recs = [mp([[ext_ts(r.randrange(0, 2 ** 32 - 2), r.randrange(0, 10 ** 9)), packfmt_cases.rand_map(r, 1) if r.random() < 0.3 else KV([])],
+                        packfmt_cases.rand_map(r, big=r.random() < 0.1)]) for _ in range(2000)]
+            rows = list(recs)
+            rows.insert(700, mp([[ext_ts(0xffffffff, 0), KV([])], packfmt_cases.rand_map(r, 1)]))
+            rows.insert(1301, mp([[ext_ts(0xfffffffe, 0), KV([])], KV([])]))
+            chunk = b"".join(rows)
+            want = ob.msgpack_to_json_format(chunk, cfg["json_format"], cfg["date_format"], b"date", esc, 0)
+            assert ob.msgpack_to_json_format(chunk, 3, cfg["date_format"], b"date", esc, 0).count(b"\n") == len(recs) == 2000
+            assert f.format(chunk) == want
             f.close()
 
 
