@@ -145,6 +145,8 @@ def lib():
     L.flbgpu_filter_host_rules.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_uint64)]
     L.flbgpu_filter_paths.restype = ctypes.c_int
     L.flbgpu_filter_paths.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_uint64)]
+    L.flbgpu_filter_dec_launch.restype = ctypes.c_int
+    L.flbgpu_filter_dec_launch.argtypes = [c_void_p, ctypes.POINTER(ctypes.c_uint64)]
     L.flbgpu_filter_regex_corners.restype = ctypes.c_uint64
     L.flbgpu_filter_regex_corners.argtypes = [c_void_p]
     L.flbgpu_rx_simulate_fx3.argtypes = [c_void_p, c_char_p, c_int, POINTER(c_int), POINTER(c_int), POINTER(c_int)]
@@ -304,6 +306,13 @@ class _Filter:
         return dict(single_pass=bool(lp & 1), three_port=bool(lp & 2), emit_time=bool(lp & 4), plain_emit=bool(lp & 8), rows_by_length=bool(lp & 16),
                     aside=dict(single_pass=bool(o[1]), three_port=bool(o[2]), emit_time=bool(o[3]), plain_emit=bool(o[4])),
                     tries=int(o[5]), returns=int(o[6]), calls=int(o[7]))
+
+    def dec_launch(self):
+        """the Decode_Field kernels of this filter_parser instance's last call (flbgpu_filter_dec_launch): lanes, bytes per scratch
+        region, rows decoded, rows that outgrew an earlier size pass's scratch, size passes"""
+        o = (ctypes.c_uint64 * 5)()
+        lib().flbgpu_filter_dec_launch(self.h, o)
+        return dict(lanes=int(o[0]), cap=int(o[1]), rows=int(o[2]), overflow=int(o[3]), passes=int(o[4]))
 
     def profile(self, enable=True):
         lib().flbgpu_filter_profile(self.h, int(enable))

@@ -13,8 +13,9 @@
 // It runs twice (CountSink for the size pass, ByteSink for the emit pass: k_parser_dec); rows it owns carry RF_DEC and are left
 // alone by k_parser_emit.  Everything here is the slow, exact path: decoders are a per-record rewrite of strings into objects,
 // not a scan.  Scratch per lane: DEC_REGIONS regions of `cap` bytes (map A, map B, two text halves, the Decode_Field object,
-// the extra-keys buffer); a region that overflows makes the call fail loudly (DecArgs::err), it is sized from the chunk's
-// longest record.
+// the extra-keys buffer; the merged map goes back into region 0); a row whose region overflows in the size pass is counted
+// (DecArgs::err) and the host runs the size pass again with twice the room before it uses any size (flbgpu.cpp run_parser_dev: the
+// first cap is a guess from the chunk's longest record, 2.25 to 4.5 bytes per byte of text are ordinary for short JSON numbers).
 // (csrc/dec.hpp -- the string backends, one template for host and device -- is included by the translation unit, outside the namespace)
 
 struct MemSink {

@@ -416,7 +416,7 @@ struct DecArgs {
     uint8_t *scratch;
     uint32_t cap;               // bytes per region
     int mode;
-    unsigned long long *err;    // rows whose scratch overflowed (the call fails)
+    unsigned long long *err;    // rows whose scratch overflowed (size pass: run again with a larger cap; emit pass: the call fails)
     unsigned long long *ndec;   // rows handled (size pass)
 };
 void launch_parser_dec(const DecArgs &a, int blocks, hipStream_t st);

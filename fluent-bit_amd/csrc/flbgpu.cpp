@@ -354,7 +354,7 @@ extern "C" int flbgpu_parser_add_decoder(flbgpu_parser *p, int as, const char *b
     if (action && *action) {
         if (!strcasecmp(action, "try_next")) act = DEC_A_TRY_NEXT;
         else if (!strcasecmp(action, "do_next")) act = DEC_A_DO_NEXT;
-        else { set_err("parser '%s': unknown decoder action '%s'", p->name.c_str(), action); return -1; }
+        // (any other word is no action, not an error: src/flb_parser_decoder.c:722-730)
     }
     const size_t kl = strlen(key);
     if (kl == 0 || kl > sizeof(p->decs.d[0].key)) { set_err("parser '%s': decoder key too long", p->name.c_str()); return -1; }
@@ -1073,6 +1073,14 @@ extern "C" int flbgpu_filter_paths(flbgpu_filter *f, uint64_t *out8) {
     return 0;
 }
 
+// the decoders' launch of the last call (run_parser_dev): lanes, bytes per scratch region, rows the last size pass handled, rows that
+// outgrew an earlier pass's scratch, size passes run
+extern "C" int flbgpu_filter_dec_launch(flbgpu_filter *f, uint64_t *out5) {
+    if (!f || !out5) return -1;
+    for (int i = 0; i < 5; i++) out5[i] = f->dec_launch[i];
+    return 0;
+}
+
 // host rules of a filter (see "host rules" below): out[0] = how many of its rules / parsers run on the host's backtracking matcher,
 // out[1] = values it has searched so far, out[2] = of these, searches that ended on the backtrack budget (answered "no match", as the
 // reference answers its own limit), out[3] = records a host parser did not take (duplicate Key_Name entries, values >= 64 KB)
@@ -1731,18 +1739,22 @@ static bool run_parser_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_
     DecArgs dca;
     int dec_blocks = 0;
     memset((void *) &dca, 0, sizeof(dca));
-    if (f->has_decoders) {
-        launch_max_row_len(row_off, n, &dm->max_row, st);
-        HIPOK(hipMemcpyAsync(&hm, dm, sizeof(hm), hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
-        // a region holds a packed map or a decoded text: 3 x the longest record + room for the field names is never reached
-        const uint64_t cap = (uint64_t) hm.max_row * 3 + 4096;
+    uint64_t dec_cap = 0;
+    // The decoders' size pass with `cap` bytes per scratch region.  The first cap of a call is a guess, not a bound: what a region
+    // holds per byte of the record depends on the rules (a JSON `1e5,` is 4 bytes of text and 9 of msgpack, `a=1 ` under Types a:float
+    // 11; Decode_Field json do_next + Decode_Field_As json merge two such copies: 4.5 x the record and more).  A row that does
+    // not fit is only counted (DecArgs::err); the caller looks at the count BEFORE it uses the sizes and runs the pass again with
+    // twice the room.  The pass is idempotent per row (it reads the record and the parser's captures, writes the row's own slots),
+    // so the second run simply covers every row again.
+    auto dec_size = [&](uint64_t cap) -> bool {
         uint64_t lanes = (n + 63) / 64 * 64;
-        const uint64_t budget = (uint64_t) 1 << 31;
+        // FLBGPU_DEC_BUDGET_MB: the scratch the lanes may share, read per call (default 2 GiB); fewer lanes, never fewer than one wave
+        uint64_t budget = (uint64_t) 1 << 31;
+        if (const char *e = getenv("FLBGPU_DEC_BUDGET_MB")) { const long long v = atoll(e); if (v >= 1 && v <= 65536) budget = (uint64_t) v << 20; }
         while (lanes > 64 && lanes * DEC_REGIONS * cap > budget) lanes = (lanes / 2 + 63) / 64 * 64;
-        if (lanes > 64 * 4096) lanes = 64 * 4096;
         if (cap > 0xFFFFFFF0ull || !f->d_dec.ensure(lanes * DEC_REGIONS * cap)) { set_err("filter_parser: no memory for the decoders' scratch"); return false; }
         dec_blocks = (int) (lanes / 64);
+        dec_cap = cap;
         dca.e.data = data; dca.e.row_off = row_off; dca.e.n = n; dca.e.cfg = f->pcfg; dca.e.parsers = f->d_parsers.as<DevParser>();
         dca.e.n_cols = in->n; dca.e.info = f->d_info.as<uint32_t>(); dca.e.caps = f->d_caps.as<uint32_t>(); dca.e.caps_stride = f->caps_stride;
         dca.e.null_mask = f->d_null.as<uint64_t>(); dca.e.out_len = f->d_len.as<uint32_t>(); dca.e.out_off = nullptr; dca.e.out = nullptr; dca.e.bytes = in->bytes;
@@ -1750,6 +1762,15 @@ static bool run_parser_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_
         dca.mode = 0; dca.err = &dm->counts[10]; dca.ndec = &dm->counts[11];
         HIPOK(hipMemsetAsync(&dm->counts[10], 0, 2 * sizeof(unsigned long long), st));
         { ProfScope ps(f, st, "k_parser_dec_size"); launch_parser_dec(dca, dec_blocks, st); }
+        f->dec_launch[0] = lanes; f->dec_launch[1] = cap; f->dec_launch[4]++;
+        return true;
+    };
+    memset(f->dec_launch, 0, sizeof(f->dec_launch));
+    if (f->has_decoders) {
+        launch_max_row_len(row_off, n, &dm->max_row, st);
+        HIPOK(hipMemcpyAsync(&hm, dm, sizeof(hm), hipMemcpyDeviceToHost, st));
+        HIPOK(hipStreamSynchronize(st));
+        if (!dec_size((uint64_t) hm.max_row * 3 + 4096)) return false;
     }
     // write offsets + the number of emitted records (what flb_mp_count_log_records would report) in one pass
     { ProfScope ps(f, st, "k_scan"); launch_scan(f->d_len.as<uint32_t>(), n, f->d_scan_tmp.as<uint64_t>(), f->d_off.as<uint64_t>(), st, &dm->counts[1]); }
@@ -1783,6 +1804,19 @@ static bool run_parser_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_
     HIPOK(hipMemcpyAsync(&total, f->d_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     HIPOK(hipMemcpyAsync(&hm, dm, sizeof(hm), hipMemcpyDeviceToHost, st));
     HIPOK(hipStreamSynchronize(st));
+    // rows that outgrew the decoders' scratch: their sizes are not known yet, so neither `total` nor the offsets are -- the size pass
+    // and the scan again with twice the room, until every row fits (or the room can no longer be had: the call fails, as before)
+    while (f->has_decoders && hm.counts[10] > 0) {
+        f->dec_launch[3] += hm.counts[10];
+        const unsigned long long over = hm.counts[10];
+        if (!dec_size(dec_cap * 2)) { set_err("filter_parser: a decoded field outgrew the decoders' scratch (%llu records) and no larger one can be had", over); return false; }
+        HIPOK(hipMemsetAsync(&dm->counts[1], 0, sizeof(unsigned long long), st));
+        { ProfScope ps(f, st, "k_scan"); launch_scan(f->d_len.as<uint32_t>(), n, f->d_scan_tmp.as<uint64_t>(), f->d_off.as<uint64_t>(), st, &dm->counts[1]); }
+        HIPOK(hipMemcpyAsync(&total, f->d_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIPOK(hipMemcpyAsync(&hm, dm, sizeof(hm), hipMemcpyDeviceToHost, st));
+        HIPOK(hipStreamSynchronize(st));
+    }
+    f->dec_launch[2] = f->has_decoders ? hm.counts[11] : 0;
     f->last_in = hm.counts[0];
     if (hm.ov_count > OV_CAP) {
         set_err("filter_parser: more than %u parsed Key_Name entries at body map index 64 and up in one chunk", OV_CAP);

@@ -215,6 +215,9 @@ struct flbgpu_filter {
     int fx_on_device = 0;             // which pair tables this filter's device copy of parser 0 holds: 0 three-port (as created), 1 four-port
     uint32_t last_path = 0;           // what the last call ran: bit 0 single pass, 1 three-port tables, 2 time lookup in k_pg_emit, 3 plain emit build
     bool has_decoders = false;        // a parser of the list has Decode_Field / Decode_Field_As rules (dec_dev.inc: k_parser_dec)
+    // the last call's decoder launch (flbgpu_filter_dec_launch): lanes, bytes per scratch region, rows decoded, rows whose scratch
+    // overflowed in a size pass that was then run again, size passes run
+    uint64_t dec_launch[5] = {0, 0, 0, 0, 0};
     // filter_grep (and the rule gate of filter_log_to_metrics)
     std::vector<flbgpu::GrepRule> rules;
     std::vector<flbgpu::TableBlob *> rule_blobs;

@@ -75,7 +75,7 @@ flbgpu_parser *flbgpu_parser_create_kv(const char *name, const char *format, con
 /* One Decode_Field / Decode_Field_As line of the parser's section -- `Decode_Field[_As] <backend> <key> [try_next | do_next]`
  * (conf/parsers.conf:44-58; src/flb_parser_decoder.c:593-776 flb_parser_decoder_list_create builds struct flb_parser.decoders from
  * them): as = 1 for Decode_Field_As, backend "json" | "escaped" | "escaped_utf8" | "mysql_quoted", action NULL / "" | "try_next" |
- * "do_next".  Call in configuration order, before the parser is handed to flbgpu_filter_parser_create; the rules then run inside
+ * "do_next" (any other word is no action, as in the reference: :722-730).  Call in configuration order, before the parser is handed to flbgpu_filter_parser_create; the rules then run inside
  * the filter exactly where flb_parser_decoder_do (:215-550) runs inside flb_parser_do (regex / logfmt / ltsv: on the packed
  * map; Format json: before the time lookup).  0, or -1 with flbgpu_last_error(). */
 int flbgpu_parser_add_decoder(flbgpu_parser *p, int as, const char *backend, const char *key, const char *action);
@@ -552,6 +552,12 @@ uint64_t flbgpu_filter_regex_corners(flbgpu_filter *f);
  * differ a lot in length), [1..4] set aside right now: single pass / three-port tables / emit-side
  * lookup / plain build, [5] tries of a build that was set aside, [6] tries that brought it back, [7] device-level calls so far. */
 int flbgpu_filter_paths(flbgpu_filter *f, uint64_t *out8);
+/* The decoders' launch of a filter_parser instance's last device-level call (Decode_Field / Decode_Field_As: csrc/dec_dev.inc).  Read only,
+ * for the tests.  out5: [0] lanes launched, [1] bytes per scratch region (the last size pass's: a pass in which a row outgrew its scratch
+ * is run again with twice the room), [2] rows the last size pass handled, [3] rows that outgrew the scratch of an earlier pass,
+ * [4] size passes run.  All zero: the call launched no decoder kernel.  FLBGPU_DEC_BUDGET_MB (read per call, default 2048): the scratch
+ * the lanes share; a smaller budget means fewer lanes (never fewer than 64), each taking several rows in turn. */
+int flbgpu_filter_dec_launch(flbgpu_filter *f, uint64_t *out5);
 /* Rules / parsers whose pattern is NOT a regular expression (look-around, atomic groups, possessive repeats, back-references, \Z \G \K; round 5: the absent operator (?~X), subexpression calls \g<..>, more than 31 groups, (?i) over non-ASCII literals and classes, \X)
  * do not fail the create calls: the device does everything but the search of that pattern, which the product's backtracking matcher
  * (csrc/rxbt.inc) runs on the host over the values the device located -- filter_grep rules, filter_log_to_metrics rules (run as a
