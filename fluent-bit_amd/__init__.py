@@ -1037,6 +1037,19 @@ class StreamTask:
             return {"k_sp_select<size>": (ms[0], int(n[0])), "k_sp_select<emit>": (ms[1], int(n[1]))}
         return {"k_sp_extract": (ms[0], int(n[0])), "k_sp_aggregate": (ms[1], int(n[1]))}
 
+    def stats(self):
+        """the group dictionary and the last do() / do_dev() (flbgpu_sp_stats), for tests: dictionary growths since create, slots,
+        dictionary entries, rows that entered a group, rows the generic kernel redid, the first row that does not decode (None: all
+        decode), passes over the chunk, the CU count the grids were sized by"""
+        L = lib()
+        L.flbgpu_sp_stats.argtypes = [c_void_p, POINTER(c_uint64)]
+        o = (c_uint64 * 8)()
+        if L.flbgpu_sp_stats(self.h, o) != 0:
+            raise RuntimeError(last_error())
+        bad = int(o[5])
+        return {"grows": int(o[0]), "slots": int(o[1]), "groups": int(o[2]), "rows_in": int(o[3]), "deferred": int(o[4]),
+                "first_bad": None if bad == 2 ** 64 - 1 else bad, "attempts": int(o[6]), "cus": int(o[7])}
+
     def close(self):
         if self.h:
             lib().flbgpu_sp_destroy(self.h)

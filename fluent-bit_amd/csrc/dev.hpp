@@ -635,16 +635,23 @@ struct SpPlan {
 // One row of 64-bit words per group; like the log_to_metrics rows every word merges with max or add, so the state does
 // not depend on the order records (or GPUs) are visited in:
 //   [0]                      max of ~(global index of the record that created the group)  -> first-seen order of package_results
-//   [1 + 4 s + 0..3]         max: ~ord(min int), ord(max int), ~ord(min float), ord(max float) of aggregated key s
-//   [A] (A = 1 + 4 nsrc)     add: records of the group (aggr_node->records)
-//   [A + 1 + s SP_SRC_ADD +] add: ints seen, non-zero floats seen, wrapping int64 sum, NaN / +Inf / -Inf counts, then the
-//                            exact fixed-point sum digits of every value (L2M_NLIMB words, digit j has weight 2^(32 j - 1074))
-constexpr int SP_SRC_MAX = 4;
-constexpr int SP_A_NINT = 0, SP_A_NFLT = 1, SP_A_ISUM = 2, SP_A_NAN = 3, SP_A_PINF = 4, SP_A_NINF = 5, SP_A_LIMB = 6;
+//   [1 + 5 s + 0..4]         max: ~ord(min int), ord(max int), ~ord(min float), ord(max float) of aggregated key s, and
+//                            ~(global index of its first non-zero float): where the reference's sum turns from int64 to double
+//   [A] (A = 1 + 5 nsrc)     add: records of the group (aggr_node->records)
+//   [A + 1 + s SP_SRC_ADD +] add: ints seen, non-zero floats seen, wrapping int64 sum, NaN / +Inf / -Inf counts, the sum of
+//                            v >> 32 over the integers AHEAD of the first float and the wrapping sum of the integers behind
+//                            it (from the two and the wrapping sum of all, the host knows how often the reference's int64
+//                            wrapped before it became a double: sp.cpp, package), then the exact fixed-point sum digits
+//                            of every value (L2M_NLIMB words, digit j has weight 2^(32 j - 1074))
+constexpr int SP_SRC_MAX = 5;
+constexpr int SP_M_FIRST_FLT = 4;
+constexpr int SP_A_NINT = 0, SP_A_NFLT = 1, SP_A_ISUM = 2, SP_A_NAN = 3, SP_A_PINF = 4, SP_A_NINF = 5, SP_A_PRE_HI = 6, SP_A_POST_ISUM = 7,
+              SP_A_LIMB = 8;
 constexpr int SP_SRC_ADD = SP_A_LIMB + 68;
 inline int sp_row_words(int nsrc) { return 1 + SP_SRC_MAX * nsrc + 1 + SP_SRC_ADD * nsrc; }
 constexpr uint32_t SP_GID_NONE = 0xFFFFFFFFu;
 constexpr uint32_t SP_GID_DEFER = 0xFFFFFFFEu;     // needs k_sp_generic (decimal string -> binary64)
+constexpr uint32_t SP_VT_MANY = 63;                // vt_col's six count bits: 63 and more entries of the name, see cnt_col
 // status bits (SpArgs::flags): inputs the reference itself does not treat in an order-independent way -> the call fails
 enum { SPF_BAD_RECORD = 1, SPF_KEY_NUL = 2, SPF_KEY_NAN = 4, SPF_FLOAT_RANGE = 8 };
 struct SpArgs {
@@ -655,16 +662,19 @@ struct SpArgs {
     L2mTable t;
     uint32_t *gid_col;               // [n]
     uint64_t *val_col;               // [nsrc][n] int64 / binary64 bits
-    uint8_t *vt_col;                 // [nsrc][n] class (0 none, 1 int, 2 float) | occurrences << 2
+    uint8_t *vt_col;                 // [nsrc][n] class (0 none, 1 int, 2 float) | occurrences << 2 (SP_VT_MANY: the count is in cnt_col)
+    uint32_t *cnt_col;               // [nsrc][n] occurrences, written only where they do not fit vt_col
     unsigned long long *first_bad;
     unsigned long long *counts;      // [0] records that entered a group, [1] records deferred to k_sp_generic
     unsigned int *col_class;         // [SP_MAX_GB] OR of (1 << class) seen in each GROUP BY column (1 int, 2 float, 4 string)
     unsigned int *flags;
+    unsigned int *seen;              // OR of 1 (a non-zero integer under an aggregated key) and 2 (a non-zero float)
 };
 struct SpAggArgs {
     const uint32_t *gid_col;
     const uint64_t *val_col;
     const uint8_t *vt_col;
+    const uint32_t *cnt_col;
     uint64_t n;
     const unsigned long long *first_bad;
     unsigned long long *rows;
@@ -674,7 +684,7 @@ struct SpAggArgs {
 };
 void launch_sp_extract(const SpArgs &a, int cus, hipStream_t st);
 void launch_sp_generic(const SpArgs &a, hipStream_t st);
-void launch_sp_aggregate(const SpAggArgs &a, int cus, hipStream_t st);
+void launch_sp_aggregate(const SpAggArgs &a, int cus, bool first_float_pass, hipStream_t st);
 
 // ---- JSON text -> msgpack (src/flb_pack.c:389-508)
 struct JsonArgs {

@@ -13,6 +13,7 @@
 // NOW() / UNIX_TIMESTAMP() / RECORD_TAG() / RECORD_TIME() are select keys of both branches (the caller's `now` stands for time(NULL)).
 // Queries outside that set (TIMESERIES_FORECAST, snapshots) are refused at create time; inputs on
 // which the reference's own result depends on the rb-tree's shape (a GROUP BY column mixing numbers and strings, NaN keys)
+// or on the order the records arrive in (NaN under MIN / MAX)
 // make the call fail instead of answering something else.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -418,7 +419,7 @@ struct Parser {
     }
 };
 
-struct SpMisc { unsigned long long first_bad; unsigned long long counts[2]; unsigned int col_class[SP_MAX_GB]; unsigned int flags; unsigned int pad; };
+struct SpMisc { unsigned long long first_bad; unsigned long long counts[2]; unsigned int col_class[SP_MAX_GB]; unsigned int flags; unsigned int seen; };
 
 }  // namespace
 
@@ -436,7 +437,11 @@ struct flbgpu_sp {
     DevBuf d_sconst;
     hipStream_t stream = nullptr;
     L2mState tab;                       // group dictionary + rows (the table part of the log_to_metrics state)
-    DevBuf d_plan, d_gid, d_val, d_vt, d_misc, d_in, d_off;
+    DevBuf d_plan, d_gid, d_val, d_vt, d_cnt, d_misc, d_in, d_off;
+    // the last flbgpu_sp_do / _do_dev (flbgpu_sp_stats): rows that entered a group, rows k_sp_generic redid, the first row that
+    // does not decode (~0: none), passes over the chunk (1 + dictionary growths + 1 when a row did not decode), CUs the grids used
+    uint64_t last_in = 0, last_defer = 0, last_bad = ~0ull, last_attempts = 0, last_groups = 0;
+    int last_cus = 0;
     uint64_t idx_base = 0;
     uint64_t records = 0;               // task->window.records
     unsigned int col_class[SP_MAX_GB] = {0, 0, 0, 0};
@@ -454,6 +459,41 @@ struct flbgpu_sp {
 };
 
 namespace {
+
+// The row stride.  k_sp_aggregate's LDS combiner (l2m_kernels.inc, L2mCombiner::upd) hashes a row word's index multiplicatively into
+// 4096 slots and gives up after four probes; the words a group keeps hot sit at the same offsets in every row, so the stride alone
+// decides whether the groups' words spread or pile up (two sources: a stride of 164 words sends a third of them to global atomics,
+// 174 none).  Up to 31 unused words behind the row: the stride with the fewest words left without a slot for 256 groups' record
+// count, value counts, integer sum and the two digits integers below 2^46 touch.
+int sp_row_stride(int nsrc) {
+    const int words = sp_row_words(nsrc);
+    int best = words;
+    size_t best_lost = ~(size_t) 0;
+    for (int W = words; W < words + 32; W++) {
+        std::vector<uint32_t> slot(4096, 0);
+        size_t lost = 0;
+        for (uint64_t g = 0; g < 256; g++) {
+            std::vector<uint64_t> hot{g * W + 1 + (uint64_t) SP_SRC_MAX * nsrc};
+            for (int s = 0; s < nsrc; s++) {
+                const uint64_t base = hot[0] + 1 + (uint64_t) SP_SRC_ADD * s;
+                for (int w : {SP_A_NINT, SP_A_NFLT, SP_A_ISUM, SP_A_LIMB + 33, SP_A_LIMB + 34}) hot.push_back(base + w);
+            }
+            for (uint64_t idx : hot) {
+                const uint32_t key = (uint32_t) idx + 1;
+                uint32_t h = (key * 2654435761u) >> 20;
+                bool placed = false;
+                for (int probe = 0; probe < 4 && !placed; probe++) {
+                    if (slot[h] == 0) slot[h] = key;
+                    placed = slot[h] == key;
+                    h = (h + 1) & 4095;
+                }
+                lost += !placed;
+            }
+        }
+        if (lost < best_lost) { best_lost = lost; best = W; }
+    }
+    return best;
+}
 
 int plan_key(flbgpu_sp *t, const KeyName &k, std::string &why) {
     SpPlan &pl = t->plan;
@@ -826,9 +866,23 @@ bool package(flbgpu_sp *t, Snapshot &sn, uint32_t now_sec, uint32_t now_nsec, st
             const uint64_t n_int = ad[SP_A_NINT], n_flt = ad[SP_A_NFLT];
             const bool is_f64 = n_flt > 0;          // a non-zero float turned nums[key].type into FLB_SP_NUM_F64
             if (k.func == F_SUM || k.func == F_AVG) {
+                // the reference adds integers as a wrapping int64 until the first non-zero float arrives and converts then
+                // (flb_sp_aggregate_func.c:27-71, flb_sp.c:1553-1561): the double starts from the WRAPPED sum S of the integers ahead
+                // of that float.  The row keeps S mod 2^64 (all integers less those behind the float) and the sum H of v >> 32 over
+                // them, so S is the one number of that residue in [2^32 H, 2^32 (H + integers)); every 2^64 it wrapped by leaves
+                // the exact digits again (2^64 is bit 18 of digit 35)
+                uint64_t limbs[L2M_NLIMB];
+                memcpy(limbs, ad + SP_A_LIMB, sizeof(limbs));
+                if (is_f64 && n_int) {
+                    const __int128 low = (__int128) (int64_t) ad[SP_A_PRE_HI] * 4294967296ll;
+                    const uint64_t res = ad[SP_A_ISUM] - ad[SP_A_POST_ISUM];
+                    const __int128 S = low + (__int128) (uint64_t) (res - (uint64_t) low);
+                    const __int128 wraps = (S + ((__int128) 1 << 63)) >> 64;
+                    limbs[35] = (uint64_t) ((int64_t) limbs[35] - (int64_t) wraps * (1ll << 18));
+                }
                 double dsum = 0;
                 int64_t isum = (int64_t) ad[SP_A_ISUM];
-                if (is_f64) dsum = bits_double(l2m_limbs_bits(ad + SP_A_LIMB, ad[SP_A_NAN], ad[SP_A_PINF], ad[SP_A_NINF]));
+                if (is_f64) dsum = bits_double(l2m_limbs_bits(limbs, ad[SP_A_NAN], ad[SP_A_PINF], ad[SP_A_NINF]));
                 if (lf) {
                     if (is_f64) dsum = dsum - (double) lf->rm_i[src] - lf->rm_f[src];
                     else isum = (int64_t) ((uint64_t) isum - (uint64_t) lf->rm_i[src]);
@@ -860,6 +914,8 @@ bool package(flbgpu_sp *t, Snapshot &sn, uint32_t now_sec, uint32_t now_nsec, st
 // a plain SELECT over one chunk: size pass, scan, emit; what leaves is copied straight into the buffer finish_do hands over
 bool run_select(flbgpu_sp *t, const flbgpu_dev_chunk *in, hipStream_t st, uint32_t now_sec, uint32_t now_nsec, flbgpu_dev_chunk *dev_out = nullptr) {
     uint64_t n = in->n;
+    t->last_in = t->last_defer = t->last_attempts = 0;
+    t->last_bad = ~0ull;
     free(t->sel_out); t->sel_out = nullptr; t->sel_bytes = 0;
     if (dev_out) memset(dev_out, 0, sizeof(*dev_out));
     t->records = 0;
@@ -903,10 +959,12 @@ bool run_select(flbgpu_sp *t, const flbgpu_dev_chunk *in, hipStream_t st, uint32
         HIPOK(hipMemcpyAsync(&hm, t->d_misc.p, sizeof(hm), hipMemcpyDeviceToHost, st));
         HIPOK(hipMemcpyAsync(&total, t->d_soff.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, st));
         HIPOK(hipStreamSynchronize(st));
+        t->last_attempts++;
         if (hm.first_bad >= n) break;
-        n = hm.first_bad;
+        t->last_bad = n = hm.first_bad;
         if (n == 0) { total = 0; hm.counts[0] = 0; break; }
     }
+    t->last_in = hm.counts[0];
     if (hm.flags & SPF_BAD_RECORD) { set_err("stream processor: a record is not [time, map] / [[time, metadata], map]"); return false; }
     t->records = hm.counts[0];
     if (total == 0) return true;
@@ -931,15 +989,20 @@ bool run_dev(flbgpu_sp *t, const flbgpu_dev_chunk *in, hipStream_t st, uint32_t 
     if (t->q.select_only) return run_select(t, in, st, now_sec, now_nsec);
     L2mState &s = t->tab;
     const SpPlan &pl = t->plan;
-    const uint64_t n = in->n;
+    uint64_t n = in->n;
+    t->last_in = t->last_defer = t->last_attempts = 0;
+    t->last_bad = ~0ull;
     if (n == 0) return true;
     const int nsrc = std::max(pl.nsrc, 1);
-    if (!t->d_gid.ensure(n * 4) || !t->d_val.ensure(n * 8 * nsrc) || !t->d_vt.ensure(n * nsrc) || !t->d_misc.ensure(sizeof(SpMisc))) return false;
+    if (!t->d_gid.ensure(n * 4) || !t->d_val.ensure(n * 8 * nsrc) || !t->d_vt.ensure(n * nsrc) || !t->d_cnt.ensure(n * 4 * nsrc) ||
+        !t->d_misc.ensure(sizeof(SpMisc))) return false;
     SpMisc hm;
     L2mCtr hc;
     const int cus = device_cus() > 0 ? device_cus() : 256;
+    t->last_cus = cus;
     for (int attempt = 0;; attempt++) {
         if (attempt > 40) { set_err("stream processor: group dictionary keeps overflowing"); return false; }
+        t->last_attempts++;
         memset(&hm, 0, sizeof(hm));
         hm.first_bad = ~0ull;
         memcpy(hm.col_class, t->col_class, sizeof(hm.col_class));
@@ -950,8 +1013,9 @@ bool run_dev(flbgpu_sp *t, const flbgpu_dev_chunk *in, hipStream_t st, uint32_t 
         a.plan = t->d_plan.as<SpPlan>();
         a.t = l2m_table_of(&s);
         a.gid_col = t->d_gid.as<uint32_t>(); a.val_col = t->d_val.as<uint64_t>(); a.vt_col = t->d_vt.as<uint8_t>();
+        a.cnt_col = t->d_cnt.as<uint32_t>();
         SpMisc *dm = t->d_misc.as<SpMisc>();
-        a.first_bad = &dm->first_bad; a.counts = dm->counts; a.col_class = dm->col_class; a.flags = &dm->flags;
+        a.first_bad = &dm->first_bad; a.counts = dm->counts; a.col_class = dm->col_class; a.flags = &dm->flags; a.seen = &dm->seen;
         { Profile ps(t, 0, st); launch_sp_extract(a, cus, st); }
         HIPOK(hipMemcpyAsync(&hm, t->d_misc.p, sizeof(hm), hipMemcpyDeviceToHost, st));
         HIPOK(hipMemcpyAsync(&hc, s.d_ctr.p, sizeof(hc), hipMemcpyDeviceToHost, st));
@@ -962,9 +1026,19 @@ bool run_dev(flbgpu_sp *t, const flbgpu_dev_chunk *in, hipStream_t st, uint32_t 
             HIPOK(hipMemcpyAsync(&hc, s.d_ctr.p, sizeof(hc), hipMemcpyDeviceToHost, st));
             HIPOK(hipStreamSynchronize(st));
         }
-        if (!hc.overflow) break;
-        if (!l2m_table_grow(&s, st)) return false;          // nothing was aggregated yet: the pass runs again
+        if (hc.overflow) {
+            if (!l2m_table_grow(&s, st)) return false;      // nothing was aggregated yet: the pass runs again
+            continue;
+        }
+        if (hm.first_bad >= n) break;
+        // a row that does not decode: msgpack_unpack_next stops there (flb_sp.c:1470).  The rows behind it were looked at all the
+        // same -- their counts, value classes and refusals are not this chunk's: the rows before it, once more (as run_select does).
+        // Groups those rows entered into the dictionary stay without a record; snapshot() passes over them
+        t->last_bad = hm.first_bad;
+        n = hm.first_bad;
+        if (n == 0) return true;
     }
+    t->last_in = hm.counts[0]; t->last_defer = hm.counts[1]; t->last_groups = hc.n_series;
     if (hm.flags) {
         set_err("stream processor: %s", (hm.flags & SPF_BAD_RECORD) ? "a record is not [time, map] / [[time, metadata], map]"
                                         : (hm.flags & SPF_KEY_NUL) ? "NUL inside a string GROUP BY value (the reference compares with strcmp)"
@@ -987,10 +1061,11 @@ bool run_dev(flbgpu_sp *t, const flbgpu_dev_chunk *in, hipStream_t st, uint32_t 
     }
     SpAggArgs g;
     g.gid_col = t->d_gid.as<uint32_t>(); g.val_col = t->d_val.as<uint64_t>(); g.vt_col = t->d_vt.as<uint8_t>(); g.n = n;
+    g.cnt_col = t->d_cnt.as<uint32_t>();
     g.first_bad = &t->d_misc.as<SpMisc>()->first_bad;
     g.rows = s.d_rows.as<unsigned long long>(); g.W = s.W; g.nsrc = pl.nsrc; g.idx_base = t->idx_base;
     g.n_series = &s.d_ctr.as<L2mCtr>()->n_series;
-    { Profile ps(t, 1, st); launch_sp_aggregate(g, cus, st); }
+    { Profile ps(t, 1, st); launch_sp_aggregate(g, cus, hm.seen == 3, st); }
     HIPOK(hipStreamSynchronize(st));
     t->idx_base += n;
     t->records += hm.counts[0];
@@ -1136,7 +1211,7 @@ extern "C" flbgpu_sp *flbgpu_sp_create(const char *sql, int str_conv) {
     t->q = p.q;
     std::string why;
     if (!compile(t, why)) { set_err("stream processor: %s: %s", why.c_str(), sql); delete t; return nullptr; }
-    t->tab.W = sp_row_words(t->plan.nsrc);
+    t->tab.W = sp_row_stride(t->plan.nsrc);
     bool ok = hipStreamCreateWithFlags(&t->stream, hipStreamNonBlocking) == hipSuccess && l2m_table_init(&t->tab) && t->d_plan.ensure(sizeof(SpPlan)) &&
               hipMemcpy(t->d_plan.p, &t->plan, sizeof(SpPlan), hipMemcpyHostToDevice) == hipSuccess;
     for (auto &e : t->ev) ok = ok && hipEventCreate(&e) == hipSuccess;
@@ -1205,7 +1280,7 @@ extern "C" void flbgpu_sp_destroy(flbgpu_sp *t) {
     if (!t) return;
     L2mState &s = t->tab;
     DevBuf *all[] = {&s.d_slot_hash, &s.d_slot_sid, &s.d_arena, &s.d_key_off, &s.d_key_len, &s.d_series_hash, &s.d_rows, &s.d_ctr,
-                     &t->d_plan, &t->d_gid, &t->d_val, &t->d_vt, &t->d_misc, &t->d_in, &t->d_off, &t->d_slen, &t->d_soff, &t->d_sout, &t->d_sconst};
+                     &t->d_plan, &t->d_gid, &t->d_val, &t->d_vt, &t->d_cnt, &t->d_misc, &t->d_in, &t->d_off, &t->d_slen, &t->d_soff, &t->d_sout, &t->d_sconst};
     for (auto *b : all) b->release();
     free(t->sel_out);
     for (auto &e : t->ev) if (e) (void) hipEventDestroy(e);
@@ -1234,6 +1309,16 @@ extern "C" const char *flbgpu_sp_key_name(const flbgpu_sp *t, int i) {
 }
 extern "C" void flbgpu_sp_set_tag(flbgpu_sp *t, const char *tag, size_t len) { if (t) t->tag.assign(tag ? tag : "", tag ? len : 0); }
 extern "C" int flbgpu_sp_select_only(const flbgpu_sp *t) { return t && t->q.select_only ? 1 : 0; }
+// a read-only view for tests: out[0] dictionary growths since create, [1] slots, [2] dictionary entries after the last call (groups of
+// the window, with or without a record), and of the last flbgpu_sp_do / _do_dev: [3] rows that entered a group (a plain SELECT: that
+// passed WHERE), [4] rows k_sp_generic redid, [5] the first row that does not decode (~0: none), [6] passes over the chunk, [7] the
+// CU count the grids were sized by
+extern "C" int flbgpu_sp_stats(const flbgpu_sp *t, uint64_t *out8) {
+    if (!t || !out8) { set_err("stream processor: null argument"); return -1; }
+    out8[0] = (uint64_t) t->tab.grows; out8[1] = t->tab.cap; out8[2] = t->last_groups; out8[3] = t->last_in; out8[4] = t->last_defer;
+    out8[5] = t->last_bad; out8[6] = t->last_attempts; out8[7] = (uint64_t) t->last_cus;
+    return 0;
+}
 extern "C" void flbgpu_sp_set_index_base(flbgpu_sp *t, uint64_t base) { if (t) t->idx_base = base; }
 
 extern "C" int flbgpu_sp_do_dev(flbgpu_sp *t, const flbgpu_dev_chunk *in, void *stream, uint32_t now_sec, uint32_t now_nsec, void **out_buf,
@@ -1276,6 +1361,7 @@ extern "C" int flbgpu_sp_do(flbgpu_sp *t, const void *data, size_t bytes, uint32
         ch.data = t->d_in.p; ch.row_off = t->d_off.as<uint64_t>(); ch.n = (uint64_t) n; ch.bytes = consumed;
         if (!run_dev(t, &ch, t->stream, now_sec, now_nsec)) return -1;
     }
+    else { t->last_in = t->last_defer = t->last_attempts = 0; t->last_bad = ~0ull; }
     return finish_do(t, now_sec, now_nsec, out_buf, out_size, records);
 }
 

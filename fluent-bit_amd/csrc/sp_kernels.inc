@@ -47,27 +47,34 @@ DEV SpVal sp_value_of(const uint8_t *v, const uint8_t *end) {
 
 // flb_sp_key_to_value (flb_sp_key.c:161-222): the FIRST entry of the body whose key is `name`; sub-keys walk nested maps
 // (subkey_to_value :103-159), first match at every level; a non-map value ignores the sub-keys.  *count = entries named `name`
-// (the callers' loops run once per such entry).
-DEV SpVal sp_lookup(const SpPlan *pl, const SpKeyRef &k, const uint8_t *map, const uint8_t *end, uint32_t *count) {
+// (the callers' loops run once per such entry): *count the string entries (a map32 holds fewer than 2^32: it cannot wrap), *bins
+// the bin-typed ones, which only the GROUP BY loop's `found` asks about -- a sum it compares with at most SP_MAX_GB, so they are
+// counted up to SP_BINS_MAX and no further.
+constexpr uint32_t SP_BINS_MAX = 7;
+DEV SpVal sp_lookup(const SpPlan *pl, const SpKeyRef &k, const uint8_t *map, const uint8_t *end, uint32_t *count, uint32_t *bins) {
     SpVal none;
     none.type = SV_NONE; none.raw = T_BAD; none.u = 0; none.s = nullptr; none.len = 0;
-    *count = 0;
+    *count = 0; *bins = 0;
     Tok m = mp_tok(map, end);
     if (m.type != T_MAP) return none;
     const uint8_t *p = m.next, *first = nullptr;
-    uint32_t cnt = 0;
+    uint32_t cnt = 0, nb = 0;
     for (uint32_t i = 0; i < m.len; i++) {
         Tok kk = mp_tok(p, end);
         const uint8_t *v = mp_skip(p, end, 2);
         if (!v) break;
         // (flb_sp_key_to_value compares key.via.str without a look at key.type, flb_sp_key.c:189, and bin shares the layout: the value
-        // is the first str-or-bin entry's.  *count: string entries in the low half (the loop over the select keys wants key.type == STR,
-        // flb_sp.c:1510), binary ones in the high half (the GROUP BY loop :1317-1326 does not look at the type either)
-        if ((kk.type == T_STR || kk.type == T_BIN) && sp_name_eq(kk.next, kk.len, pl->blob + k.name_off, k.name_len)) { if (!first) first = v; cnt += kk.type == T_STR ? 1u : 0x10000u; }
+        // is the first str-or-bin entry's.  *count: string entries (the loop over the select keys wants key.type == STR,
+        // flb_sp.c:1510), *bins: binary ones (the GROUP BY loop :1317-1326 does not look at the type either)
+        if ((kk.type == T_STR || kk.type == T_BIN) && sp_name_eq(kk.next, kk.len, pl->blob + k.name_off, k.name_len)) {
+            if (!first) first = v;
+            if (kk.type == T_STR) cnt++;
+            else if (nb < SP_BINS_MAX) nb++;
+        }
         p = mp_skip(v, end, 2);
         if (!p) break;
     }
-    *count = cnt;
+    *count = cnt; *bins = nb;
     if (!first) return none;
     Tok t = mp_tok(first, end);
     if (t.type == T_MAP && k.nsub > 0) {
@@ -101,12 +108,14 @@ constexpr int SP_FAST_KEYS = 6;
 struct SpHits {
     bool fast;
     const uint8_t *first[SP_FAST_KEYS];
-    uint32_t cnt[SP_FAST_KEYS];
+    uint32_t cnt[SP_FAST_KEYS];                                   // string entries per key, as sp_lookup's *count
+    uint32_t bins;                                                // bin-typed entries, four bits per key, each pinned at SP_BINS_MAX
 };
 // false: the body does not decode.  *walk_end = first byte after the map
 DEV bool sp_walk(const SpPlan *pl, const uint8_t *map, const uint8_t *end, SpHits &h, const uint8_t **walk_end) {
     #pragma unroll
     for (int k = 0; k < SP_FAST_KEYS; k++) { h.first[k] = nullptr; h.cnt[k] = 0; }
+    h.bins = 0;
     Tok m = mp_tok(map, end);
     if (m.type != T_MAP) return false;
     const uint8_t *p = m.next;
@@ -120,7 +129,8 @@ DEV bool sp_walk(const SpPlan *pl, const uint8_t *map, const uint8_t *end, SpHit
             for (int k = 0; k < SP_FAST_KEYS; k++) {
                 if (k < nk && kk.len == pl->keys[k].name_len && sp_name_eq(kk.next, kk.len, pl->blob + pl->keys[k].name_off, kk.len)) {
                     if (!h.first[k]) h.first[k] = v;
-                    h.cnt[k] += kk.type == T_STR ? 1u : 0x10000u;
+                    if (kk.type == T_STR) h.cnt[k]++;
+                    else if (((h.bins >> (4 * k)) & 15u) < SP_BINS_MAX) h.bins += 1u << (4 * k);
                 }
             }
         }
@@ -163,13 +173,14 @@ DEV SpVal sp_first_value(const SpPlan *pl, const SpKeyRef &k, const uint8_t *fir
     return sp_value_of(first, end);
 }
 
-DEV SpVal sp_get(const SpPlan *pl, const SpHits &h, uint32_t key, const uint8_t *map, const uint8_t *end, uint32_t *count) {
-    if (!h.fast) return sp_lookup(pl, pl->keys[key], map, end, count);
+DEV SpVal sp_get(const SpPlan *pl, const SpHits &h, uint32_t key, const uint8_t *map, const uint8_t *end, uint32_t *count, uint32_t *bins) {
+    if (!h.fast) return sp_lookup(pl, pl->keys[key], map, end, count, bins);
     const uint8_t *f = h.first[0];
     uint32_t c = h.cnt[0];
     #pragma unroll
     for (int k = 1; k < SP_FAST_KEYS; k++) if (key == (uint32_t) k) { f = h.first[k]; c = h.cnt[k]; }
     *count = c;
+    *bins = (h.bins >> (4 * key)) & 15u;
     return sp_first_value(pl, pl->keys[key], f, end);
 }
 
@@ -266,9 +277,9 @@ DEV SpVal sp_leaf(const SpPlan *pl, const SpHits &h, uint32_t li, const uint8_t 
     const SpLeaf &lf = pl->leaf[li];
     SpVal r;
     r.type = SV_NONE; r.raw = T_BAD; r.u = lf.v; r.s = nullptr; r.len = 0;
-    uint32_t cnt;
+    uint32_t cnt, bins;
     switch (lf.kind) {
-    case SPL_KEY: return sp_get(pl, h, lf.key, map, end, &cnt);
+    case SPL_KEY: return sp_get(pl, h, lf.key, map, end, &cnt, &bins);
     case SPL_INT: r.type = SV_INT; break;
     case SPL_FLOAT: r.type = SV_FLOAT; break;
     case SPL_STR: r.type = SV_STR; r.s = (const uint8_t *) pl->blob + lf.str_off; r.len = lf.str_len; break;
@@ -276,7 +287,7 @@ DEV SpVal sp_leaf(const SpPlan *pl, const SpHits &h, uint32_t li, const uint8_t 
     case SPL_NULL: r.type = SV_NULL; break;
     case SPL_TIME: r.type = SV_FLOAT; r.u = (uint64_t) __double_as_longlong(ts); break;
     case SPL_CONTAINS: {                                          // cb_contains: NULL in, NULL out; else true
-        SpVal v = sp_get(pl, h, lf.key, map, end, &cnt);
+        SpVal v = sp_get(pl, h, lf.key, map, end, &cnt, &bins);
         if (v.type != SV_NONE) { r.type = SV_BOOL; r.u = 1; }
         break;
     }
@@ -396,7 +407,7 @@ DEV int sp_to_number(const SpVal &v, int conv, int64_t *iv, uint64_t *fb, unsign
 }
 
 template <bool GENERIC>
-DEV void sp_record(const SpArgs &a, uint64_t r, const uint8_t *rec, const uint8_t *rec_end, uint32_t &n_in, uint32_t &n_defer) {
+DEV void sp_record(const SpArgs &a, uint64_t r, const uint8_t *rec, const uint8_t *rec_end, uint32_t &n_in, uint32_t &n_defer, uint32_t &seen) {
     const SpPlan *pl = a.plan;
     uint32_t gid = SP_GID_NONE;
     bool defer = false;
@@ -423,15 +434,15 @@ DEV void sp_record(const SpArgs &a, uint64_t r, const uint8_t *rec, const uint8_
     if (pass && !defer) {
         SpTuple tp;
         tp.n = pl->ngb;
-        uint32_t found = 0;
+        uint64_t found = 0;
         #pragma unroll
         for (int g = 0; g < SP_MAX_GB; g++) {
             tp.cls[g] = 'i'; tp.u[g] = 0; tp.s[g] = nullptr; tp.len[g] = 0;
             if (g >= pl->ngb) continue;
-            uint32_t cnt = 0;
-            SpVal v = sp_get(pl, h, pl->gb_key[g], map, end, &cnt);
+            uint32_t cnt = 0, bins = 0;
+            SpVal v = sp_get(pl, h, pl->gb_key[g], map, end, &cnt, &bins);
             if (v.type == SV_NONE) continue;
-            found += (cnt & 0xFFFFu) + (cnt >> 16);
+            found += (uint64_t) cnt + bins;
             int64_t iv = 0;
             uint64_t fb = 0;
             const int k = sp_to_number<GENERIC>(v, pl->str_conv, &iv, &fb, a.flags, &defer);
@@ -447,7 +458,7 @@ DEV void sp_record(const SpArgs &a, uint64_t r, const uint8_t *rec, const uint8_
             else if (v.raw == T_BOOL) tp.u[g] = v.u;
         }
         if (defer) { }
-        else if (found < (uint32_t) pl->ngb) pass = false;
+        else if (found < (uint64_t) pl->ngb) pass = false;
         else {
             if (pl->ngb > 0) {
                 #pragma unroll
@@ -464,9 +475,8 @@ DEV void sp_record(const SpArgs &a, uint64_t r, const uint8_t *rec, const uint8_
     // (a deferred record is redone from scratch by k_sp_generic; a dictionary entry it made here is the one it will find)
     if (pass && !defer && gid != SP_GID_NONE) {
         for (int s = 0; s < pl->nsrc && !defer; s++) {
-            uint32_t cnt = 0;
-            SpVal v = sp_get(pl, h, pl->src_key[s], map, end, &cnt);
-            cnt &= 0xFFFFu;
+            uint32_t cnt = 0, bins = 0;                             // (the string entries: the loop over the select keys)
+            SpVal v = sp_get(pl, h, pl->src_key[s], map, end, &cnt, &bins);
             if (v.type == SV_NONE || cnt == 0) continue;
             int64_t iv = 0;
             uint64_t fb = 0;
@@ -474,7 +484,9 @@ DEV void sp_record(const SpArgs &a, uint64_t r, const uint8_t *rec, const uint8_
             if (k == 0) continue;
             if (k == 2 && (fb & ~nc::DBL_SIGN) == 0) { k = 1; iv = 0; }     // dval == 0.0: the reference adds ival (0)
             a.val_col[(uint64_t) s * a.n + r] = k == 1 ? (uint64_t) iv : fb;
-            a.vt_col[(uint64_t) s * a.n + r] = (uint8_t) (k | ((cnt > 63 ? 63 : cnt) << 2));
+            seen |= k == 2 ? 2u : iv != 0 ? 1u : 0u;
+            a.vt_col[(uint64_t) s * a.n + r] = (uint8_t) (k | ((cnt >= SP_VT_MANY ? SP_VT_MANY : cnt) << 2));
+            if (cnt >= SP_VT_MANY) a.cnt_col[(uint64_t) s * a.n + r] = cnt;
         }
         if (!defer) n_in++;
     }
@@ -491,7 +503,7 @@ __global__ void __launch_bounds__(SP_BLOCK) k_sp_extract(SpArgs a) {
     const uint64_t wave_id = ((uint64_t) blockIdx.x * blockDim.x + threadIdx.x) >> 6;
     const uint64_t nwaves = ((uint64_t) gridDim.x * blockDim.x) >> 6;
     const uint8_t *data_end = a.data + a.bytes;
-    uint32_t n_in = 0, n_defer = 0;
+    uint32_t n_in = 0, n_defer = 0, seen = 0;
     for (uint64_t base = wave_id * 64; base < a.n; base += nwaves * 64) {
         const uint64_t r = base + lane;
         const uint32_t cnt = (uint32_t) ((a.n - base) < 64 ? (a.n - base) : 64);
@@ -532,29 +544,31 @@ __global__ void __launch_bounds__(SP_BLOCK) k_sp_extract(SpArgs a) {
                 }
                 // (two call sites, round 6: every pointer of the second one comes from the tile, so its loads are LDS reads -- with ONE
                 // call behind a select between the chunk and the tile they were flat loads through the aperture, a record's every byte)
-                else if (direct) sp_record<false>(a, r, a.data + o0, a.data + o1, n_in, n_defer);
+                else if (direct) sp_record<false>(a, r, a.data + o0, a.data + o1, n_in, n_defer, seen);
                 else {
                     LDS_AS const uint8_t *lrec = tile + align + (uint32_t) (o0 - g0);
-                    sp_record<false>(a, r, (const uint8_t *) lrec, (const uint8_t *) (lrec + (uint32_t) (o1 - o0)), n_in, n_defer);
+                    sp_record<false>(a, r, (const uint8_t *) lrec, (const uint8_t *) (lrec + (uint32_t) (o1 - o0)), n_in, n_defer, seen);
                 }
             }
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
             lo += m;
         }
     }
-    for (int o = 32; o > 0; o >>= 1) { n_in += __shfl_down(n_in, o, 64); n_defer += __shfl_down(n_defer, o, 64); }
+    for (int o = 32; o > 0; o >>= 1) { n_in += __shfl_down(n_in, o, 64); n_defer += __shfl_down(n_defer, o, 64); seen |= __shfl_down(seen, o, 64); }
+    if (lane == 0 && seen) atomicOr(a.seen, seen);
     if (lane == 0 && n_in) atomicAdd(&a.counts[0], (unsigned long long) n_in);
     if (lane == 0 && n_defer) atomicAdd(&a.counts[1], (unsigned long long) n_defer);
 }
 
 // the records k_sp_extract deferred (a numeric string with a decimal point somewhere on their path), one per lane from HBM
 __global__ void __launch_bounds__(64) k_sp_generic(SpArgs a) {
-    uint32_t n_in = 0, n_defer = 0;
+    uint32_t n_in = 0, n_defer = 0, seen = 0;
     for (uint64_t r = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; r < a.n; r += (uint64_t) gridDim.x * blockDim.x) {
         if (a.gid_col[r] != SP_GID_DEFER) continue;
-        sp_record<true>(a, r, a.data + a.row_off[r], a.data + a.row_off[r + 1], n_in, n_defer);
+        sp_record<true>(a, r, a.data + a.row_off[r], a.data + a.row_off[r + 1], n_in, n_defer, seen);
     }
-    for (int o = 32; o > 0; o >>= 1) n_in += __shfl_down(n_in, o, 64);
+    for (int o = 32; o > 0; o >>= 1) { n_in += __shfl_down(n_in, o, 64); seen |= __shfl_down(seen, o, 64); }
+    if ((threadIdx.x & 63) == 0 && seen) atomicOr(a.seen, seen);
     if ((threadIdx.x & 63) == 0 && n_in) atomicAdd(&a.counts[0], (unsigned long long) n_in);
 }
 
@@ -562,15 +576,32 @@ __global__ void __launch_bounds__(64) k_sp_generic(SpArgs a) {
 DEV unsigned long long sp_ord_i(int64_t v) { return (unsigned long long) v ^ 0x8000000000000000ull; }
 DEV unsigned long long sp_ord_f(uint64_t bits) { return (bits >> 63) ? ~bits : (bits | 0x8000000000000000ull); }
 
-// v = M * 2^E (M < 2^64) into the fixed-point digits at `lrow`
-DEV void sp_add_digits(L2mCombiner<false> &cb, uint64_t lrow, uint64_t M, int64_t E, bool neg) {
+// mult times v = M * 2^E (M < 2^64) into the fixed-point digits at `lrow` (a digit is below 2^32 and so is mult: the product of
+// the two is what mult additions of the digit leave in the word)
+DEV void sp_add_digits(L2mCombiner<false> &cb, uint64_t lrow, uint64_t M, int64_t E, bool neg, uint64_t mult) {
     const uint32_t s = (uint32_t) (E + 1074), j = s >> 5, sh = s & 31;
     const uint64_t lo = M << sh, hi = sh ? (M >> (64 - sh)) : 0;
-    const uint64_t d0 = lo & 0xFFFFFFFFull, d1 = lo >> 32, d2 = hi & 0xFFFFFFFFull, d3 = hi >> 32;
+    const uint64_t d0 = (lo & 0xFFFFFFFFull) * mult, d1 = (lo >> 32) * mult, d2 = (hi & 0xFFFFFFFFull) * mult, d3 = (hi >> 32) * mult;
     if (d0) cb.add(lrow + j, neg ? 0 - d0 : d0);
     if (d1) cb.add(lrow + j + 1, neg ? 0 - d1 : d1);
     if (d2) cb.add(lrow + j + 2, neg ? 0 - d2 : d2);
     if (d3) cb.add(lrow + j + 3, neg ? 0 - d3 : d3);
+}
+
+// the global index of every (group, aggregated key)'s first non-zero float, ahead of k_sp_aggregate: run for the chunks that hold
+// both such floats and non-zero integers -- the integers ahead of it are the ones the reference added as an int64
+__global__ void __launch_bounds__(256) k_sp_first_float(SpAggArgs a) {
+    const uint64_t lim = *a.first_bad < a.n ? *a.first_bad : a.n;
+    for (uint64_t i = (uint64_t) blockIdx.x * blockDim.x + threadIdx.x; i < lim; i += (uint64_t) gridDim.x * blockDim.x) {
+        const uint32_t gid = a.gid_col[i];
+        if (gid == SP_GID_NONE) continue;
+        const unsigned long long o = ~(a.idx_base + i);
+        for (int s = 0; s < a.nsrc; s++) {
+            if ((a.vt_col[(uint64_t) s * a.n + i] & 3) != 2) continue;
+            unsigned long long *w = &a.rows[(uint64_t) gid * a.W + 1 + (uint64_t) SP_SRC_MAX * s + SP_M_FIRST_FLT];
+            if (o > *w) atomicMax(w, o);
+        }
+    }
 }
 
 __global__ void __launch_bounds__(L2M_AGG_BLOCK) k_sp_aggregate(SpAggArgs a) {
@@ -590,8 +621,9 @@ __global__ void __launch_bounds__(L2M_AGG_BLOCK) k_sp_aggregate(SpAggArgs a) {
         cb.add(row + A, 1);
         for (int s = 0; s < a.nsrc; s++) {
             const uint32_t vt = a.vt_col[(uint64_t) s * a.n + i];
-            const uint32_t cls = vt & 3, mult = vt >> 2;
+            const uint32_t cls = vt & 3;
             if (!cls) continue;
+            const uint64_t mult = (vt >> 2) == SP_VT_MANY ? a.cnt_col[(uint64_t) s * a.n + i] : (vt >> 2);
             const uint64_t v = a.val_col[(uint64_t) s * a.n + i];
             const uint64_t mx = row + 1 + (uint64_t) SP_SRC_MAX * s, base = row + A + 1 + (uint64_t) SP_SRC_ADD * s;
             if (cls == 1) {
@@ -603,11 +635,17 @@ __global__ void __launch_bounds__(L2M_AGG_BLOCK) k_sp_aggregate(SpAggArgs a) {
                 if (o > a.rows[mx + 1]) atomicMax(&a.rows[mx + 1], o);
                 if (iv != 0) {
                     const uint64_t M = iv < 0 ? (uint64_t) 0 - (uint64_t) iv : (uint64_t) iv;
-                    for (uint32_t q = 0; q < mult; q++) sp_add_digits(cb, base + SP_A_LIMB, M, 0, iv < 0);
+                    sp_add_digits(cb, base + SP_A_LIMB, M, 0, iv < 0, mult);
+                    // ahead of the group's first float (no float yet: the word is 0) the reference adds it as an int64, behind it as a
+                    // double: v >> 32 of the former (nothing for [0, 2^32)), the wrapping sum of the latter (sp.cpp, package)
+                    const unsigned long long ff = a.rows[mx + SP_M_FIRST_FLT];
+                    if (~gidx > ff) { if (iv >> 32) cb.add(base + SP_A_PRE_HI, (unsigned long long) (iv >> 32) * mult); }
+                    else cb.add(base + SP_A_POST_ISUM, (unsigned long long) iv * mult);
                 }
             }
             else {
                 cb.add(base + SP_A_NFLT, mult);
+                if (~gidx > a.rows[mx + SP_M_FIRST_FLT]) atomicMax(&a.rows[mx + SP_M_FIRST_FLT], ~gidx);
                 const uint64_t mag = v & ~nc::DBL_SIGN;
                 if (mag > nc::DBL_INF_BITS) cb.add(base + SP_A_NAN, mult);
                 else {
@@ -619,7 +657,7 @@ __global__ void __launch_bounds__(L2M_AGG_BLOCK) k_sp_aggregate(SpAggArgs a) {
                         uint64_t M;
                         int64_t E;
                         nc::bits_to_me(mag, false, M, E);
-                        for (uint32_t q = 0; q < mult; q++) sp_add_digits(cb, base + SP_A_LIMB, M, E, (v & nc::DBL_SIGN) != 0);
+                        sp_add_digits(cb, base + SP_A_LIMB, M, E, (v & nc::DBL_SIGN) != 0, mult);
                     }
                 }
             }
@@ -666,7 +704,7 @@ void launch_sp_generic(const SpArgs &a, hipStream_t st) {
     if (grid == 0) grid = 1;
     hipLaunchKernelGGL(k_sp_generic, dim3((unsigned) grid), dim3(64), 0, st, a);
 }
-void launch_sp_aggregate(const SpAggArgs &a, int cus, hipStream_t st) {
+void launch_sp_aggregate(const SpAggArgs &a, int cus, bool first_float_pass, hipStream_t st) {
     static std::atomic<bool> attr_set{false};
     const size_t lds = (size_t) L2M_AGG_SLOTS * 12;
     if (!attr_set) { (void) hipFuncSetAttribute((const void *) k_sp_aggregate, hipFuncAttributeMaxDynamicSharedMemorySize, (int) lds); attr_set = true; }
@@ -674,6 +712,7 @@ void launch_sp_aggregate(const SpAggArgs &a, int cus, hipStream_t st) {
     uint64_t grid = (uint64_t) cus * 2;
     if (grid > want) grid = want;
     if (grid == 0) grid = 1;
+    if (first_float_pass) hipLaunchKernelGGL(k_sp_first_float, dim3((unsigned) grid), dim3(256), 0, st, a);
     hipLaunchKernelGGL(k_sp_aggregate, dim3((unsigned) grid), dim3(L2M_AGG_BLOCK), lds, st, a);
     hipLaunchKernelGGL(k_sp_normalize, dim3(64), dim3(256), 0, st, a);
 }

@@ -82,7 +82,7 @@ template <bool COUNT, class S> DEV uint32_t sp_select_pairs(const SpSelArgs &a, 
             uint32_t c = h.cnt[0];
             #pragma unroll
             for (int k = 1; k < SP_FAST_KEYS; k++) if (sel.key == (uint32_t) k) { f = h.first[k]; c = h.cnt[k]; }
-            const uint32_t n = c & 0xFFFFu;
+            const uint32_t n = c;                                    // the string entries (sp_lookup)
             if (n && !COUNT) {
                 const uint8_t *val = sp_value_from_first(pl, kr, f, end);
                 for (uint32_t e = 0; e < n; e++) {

@@ -793,6 +793,11 @@ int flbgpu_sp_timer_all_reduce(flbgpu_sp *t, void *rccl_comm, void *stream, uint
                                size_t *out_size);
 /* event-timed kernel milliseconds / launches since the last call: [0] k_sp_extract, [1] k_sp_aggregate (+ normalize) */
 void flbgpu_sp_profile(flbgpu_sp *t, int enable, double *ms2, uint64_t *launches2);
+/* a read-only view for tests: [0] dictionary growths since create, [1] dictionary slots, [2] dictionary entries after the last call,
+ * and of the last flbgpu_sp_do / _do_dev: [3] rows that entered a group (a SELECT without aggregation functions: that passed WHERE),
+ * [4] rows redone by the generic kernel (a decimal string on their path), [5] the first row that does not decode (UINT64_MAX: none),
+ * [6] passes over the chunk (1 + dictionary growths, + 1 when a row did not decode), [7] the CU count the grids were sized by */
+int flbgpu_sp_stats(const flbgpu_sp *t, uint64_t *out8);
 
 /* ---- record boundary discovery (flb_log_event_decoder_next loop, src/flb_log_event_decoder.c:342) --
  * Walks concatenated msgpack objects in host memory; fills row_off[0..n] (capacity cap entries).
