@@ -96,6 +96,17 @@ def lib():
     L.flbgpu_expect_failure_text.argtypes = [c_void_p, c_uint64, c_char_p, c_size_t]
     L.flbgpu_expect_text_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_char_p, c_size_t,
                                            c_char_p, c_size_t]
+    L.flbgpu_filter_kubernetes_create.restype = c_void_p
+    L.flbgpu_filter_kubernetes_create.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p)]
+    L.flbgpu_kubernetes_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
+    L.flbgpu_kubernetes_set_meta.argtypes = [c_void_p, c_char_p, c_size_t, c_char_p, c_size_t]
+    L.flbgpu_kubernetes_set_tag.argtypes = [c_void_p, c_char_p, c_int]
+    L.flbgpu_kubernetes_tag_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_int, c_char_p, c_size_t]
+    L.flbgpu_kubernetes_meta_check.argtypes = [c_char_p, c_size_t, c_char_p, c_size_t, c_char_p, c_size_t]
+    L.flbgpu_kubernetes_counters.restype = None
+    L.flbgpu_kubernetes_counters.argtypes = [c_void_p, POINTER(c_uint64)]
+    L.flbgpu_kubernetes_layout.restype = None
+    L.flbgpu_kubernetes_layout.argtypes = [c_void_p, POINTER(c_uint64)]
     L.flbgpu_filter_rewrite_tag_create.restype = c_void_p
     L.flbgpu_filter_rewrite_tag_create.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p)]
     L.flbgpu_rewrite_tag_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
@@ -539,6 +550,58 @@ class RtagEmitted(ctypes.Structure):
 
 
 RTAG_EMIT_CB = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_int, c_void_p, c_size_t)
+
+
+class FilterKubernetes(_PropsFilter):
+    """filter_kubernetes, the per-record half: props = [(name, value), ...], e.g. [("merge_log", "on"), ("keep_log", "off")]
+    (plugins/filter_kubernetes/kubernetes.c).  The metadata comes from set_meta (the cache entries) or set_tag (use_tag_for_meta)"""
+    _CREATE = "flbgpu_filter_kubernetes_create"
+    _COUNTERS = "flbgpu_kubernetes_counters"
+
+    def counters(self):
+        """(records merged, records excluded, records under a counted deviation, size/emit mismatches) since the filter was created
+        (flb_gpu.h flbgpu_kubernetes_counters)"""
+        return self._counters()
+
+    def set_meta(self, pod_entry=None, ns_entry=None):
+        """the cache entries of the following calls (bytes or None); raises ValueError where the library refuses"""
+        pod, ns = (None if x is None else bytes(x) for x in (pod_entry, ns_entry))
+        if lib().flbgpu_kubernetes_set_meta(self.h, pod, len(pod) if pod else 0, ns, len(ns) if ns else 0) != 0:
+            raise ValueError(last_error())
+
+    def set_tag(self, tag):
+        """use_tag_for_meta: 0, or -1 where the tag gives no metadata (the following calls answer NOTOUCH)"""
+        tag = _b(tag)
+        return lib().flbgpu_kubernetes_set_tag(self.h, tag, len(tag))
+
+    def layout(self):
+        """dict(tail_bytes, in_lds, lds_bytes): how the appended tail is placed (flb_gpu.h flbgpu_kubernetes_layout)"""
+        o = (c_uint64 * 3)()
+        lib().flbgpu_kubernetes_layout(self.h, o)
+        return dict(tail_bytes=int(o[0]), in_lds=bool(o[1]), lds_bytes=int(o[2]))
+
+
+def kubernetes_parse_check(props):
+    """the configuration as one line of text (host only); raises ValueError where create refuses"""
+    return _parse_check("flbgpu_kubernetes_parse_check", props, 1 << 17)
+
+
+def kubernetes_tag_check(props, tag):
+    """the pod entry set_tag would build from `tag` under props (host only, bytes); raises ValueError where set_tag answers -1"""
+    buf = ctypes.create_string_buffer(1 << 17)
+    tag = _b(tag)
+    if lib().flbgpu_kubernetes_tag_check(*_props(props), tag, len(tag), buf, len(buf)) != 0:
+        raise ValueError(last_error())
+    return bytes.fromhex(buf.value.decode())
+
+
+def kubernetes_meta_check(pod_entry=None, ns_entry=None):
+    """what set_meta would keep of two cache entries as one line of text (host only); raises ValueError where it refuses"""
+    pod, ns = (None if x is None else bytes(x) for x in (pod_entry, ns_entry))
+    buf = ctypes.create_string_buffer((len(pod or b"") + len(ns or b"")) * 2 + 256)
+    if lib().flbgpu_kubernetes_meta_check(pod, len(pod) if pod else 0, ns, len(ns) if ns else 0, buf, len(buf)) != 0:
+        raise ValueError(last_error())
+    return buf.value.decode()
 
 
 class FilterRewriteTag(_PropsFilter):

@@ -351,6 +351,64 @@ int flbgpu_expect_failure_text(flbgpu_filter *f, uint64_t i, char *buf, size_t c
 int flbgpu_expect_text_check(int nprops, const char *const *names, const char *const *values, uint64_t rule, uint32_t kind, uint32_t vtype,
                              const void *val, size_t val_len, char *buf, size_t cap);
 
+/* ---- filter_kubernetes, the per-record half: replaces cb_kube_filter / pack_map_content / merge_log_handler ----
+ * plugins/filter_kubernetes/kubernetes.c:112-137 (get_stream), 139-161 (value_trim_size), 163-247 (merge_log_handler), 318-644
+ * (pack_map_content), 646-872 (one call); src/flb_pack.c:389-508 (flb_pack_json_recs).  The metadata half (kube_meta.c: the API
+ * server client, its cache and TTLs) stays with the caller: the filter is handed the cache entries flb_kube_meta_get (:692) would
+ * answer a hit with (flbgpu_kubernetes_set_meta), or builds the pod entry from the tag (use_tag_for_meta, flbgpu_kubernetes_set_tag).
+ * (names[i], values[i]) are the instance's properties, names without case, bools as flb_utils_bool reads them:
+ *   merge_log (false), keep_log (true), merge_log_trim (true), merge_log_key (none), kube_tag_prefix (kube.var.log.containers.),
+ *   use_tag_for_meta (false) are read.  Every other name of the plugin's config map (:905-1320) is accepted and not looked at: it
+ *   configures the metadata half or decides what the reference writes into an entry, and entries arrive finished.
+ * Every record the decoder hands on goes out as 92 92 d7 00 <sec> <nsec>, an empty map32 for the metadata and a map32 body (the input's metadata is not copied;
+ * group markers are stepped over): the body's own entries re-packed in order; under merge_log the first key of 3 bytes `log` (STR or
+ * BIN) is looked at -- a MAP value merges its entries, a STR value goes through flb_pack_json_recs (one record, an object; what
+ * follows must not parse as a second value) and merges the pairs, each top-level STR value cut by value_trim_size under
+ * merge_log_trim -- in place, or under merge_log_key as a nested map32 when there is at least one entry (a parsed object that opens 64
+ * containers inside a value has none: the stock build's msgpack-c unpacks 64, cmake/msgpack.cmake:11).  The `log` entry stays as it is (MAP with keep_log on; a STR that did not parse with
+ * keep_log off), goes out as key + STR of the same bytes (keep_log on, STR), or goes (merged with keep_log off; any other value type
+ * with keep_log off).  Then "kubernetes" + the pod map and "kubernetes_namespace" + the namespace map, each when set and not empty.
+ * Records whose stream (the first STR key strncmp calls "stream"; its value a prefix of "stdout", then of "stderr") the pod's
+ * properties exclude are dropped.  The call answers MODIFIED (an empty buffer when nothing is left), NOTOUCH when a time the
+ * EventTime cannot hold is met or the last set_tag failed.  create answers NULL + last_error for: an unknown property, a property
+ * set twice, a bool that is none, use_journal on, dummy_meta on, merge_parser, regex_parser, a merge_log_key of 32768 bytes or
+ * more, `${` in a value.  The test switch FLBGPU_KUBE_LDS_BLOB=<bytes>, read at create, lowers the LDS budget of the appended tail.
+ * Runs through flbgpu_filter_run[_dev], flbgpu_filter_chain_run[_dev], flbgpu_filter_last_counts (records decoded / records
+ * emitted) and flbgpu_filter_destroy. */
+flbgpu_filter *flbgpu_filter_kubernetes_create(int nprops, const char *const *names, const char *const *values);
+/* host only, no device: the configuration as one line of text --
+ * "merge_log=<0|1>;keep_log=<0|1>;trim=<0|1>;merge_log_key=<hex|->;tag_meta=<0|1>;prefix=<hex>" -- 0, or -1 + last_error where
+ * create refuses */
+int flbgpu_kubernetes_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap);
+/* the metadata of the following calls, where flb_kube_meta_get answers a cache hit.  pod_entry: what lookup_pod_meta reads from the
+ * hash table (kube_meta.c:2463-2494) -- one msgpack object, optionally followed by the properties array of flb_kube_prop_pack
+ * (kube_property.c:252-305) [stdout_parser | nil, stderr_parser | nil, stdout_exclude, stderr_exclude]; ns_entry: one msgpack object
+ * (lookup_namespace_meta).  NULL / 0: no buffer, the key is not appended.  Only the first object of each entry is appended.  The
+ * filter keeps its own copy, on the host and in HBM; the default is no metadata.  -1 + last_error for an entry whose first object
+ * does not decode, a properties array of another shape, a parser name in it (there is no parser registry here), an entry over 1 MiB;
+ * the metadata set before stays then. */
+int flbgpu_kubernetes_set_meta(flbgpu_filter *f, const void *pod_entry, size_t pod_len, const void *ns_entry, size_t ns_len);
+/* use_tag_for_meta on only: parse_regex_tag_data's tag branch and merge_meta_from_tag (kube_meta.c:1785-1811, 651-691, 1147-1200) on
+ * the host, once per tag -- the tag behind kube_tag_prefix is searched with KUBE_TAG_TO_REGEX (kube_regex.h:25) and the groups
+ * pod_name, namespace_name, container_name, docker_id that are not empty become the pod entry (a map32 of up to four pairs, no
+ * properties, no namespace entry).  0; -1 + last_error when prefix_len + 1 >= tag_len, on no match and on a spent backtrack budget:
+ * every following call answers NOTOUCH until a set_tag succeeds (as a filter does before its first set_tag). */
+int flbgpu_kubernetes_set_tag(flbgpu_filter *f, const char *tag, int tag_len);
+/* host only, no device and no filter: what set_tag would make of a tag under these properties -- the pod entry in hex -- and what
+ * set_meta would keep of two entries -- "pod=<hex|->;ns=<hex|->;stdout_exclude=<0|1>;stderr_exclude=<0|1>", the first objects.  0, or
+ * -1 + last_error where set_tag / set_meta answer -1 */
+int flbgpu_kubernetes_tag_check(int nprops, const char *const *names, const char *const *values, const char *tag, int tag_len, char *desc, size_t cap);
+int flbgpu_kubernetes_meta_check(const void *pod_entry, size_t pod_len, const void *ns_entry, size_t ns_len, char *desc, size_t cap);
+/* since the filter was created, over the calls that answered MODIFIED: out[0] records whose `log` was merged, out[1] records the
+ * stream properties excluded, out[2] records where the reference reads another member of the object's union (a `stream` value that
+ * is neither STR nor BIN: the device answers "unknown"; a numeric key whose low word is 3 where `log` is looked for: the device
+ * never matches it), out[3] rows whose emitted length differed from their sized length (always 0; the emit pass never stores
+ * outside a row's room, and a call that counts one answers NOTOUCH) */
+void flbgpu_kubernetes_counters(flbgpu_filter *f, uint64_t out[4]);
+/* how the appended tail is placed: out[0] its bytes (keys and both maps), out[1] 1 when the kernels stage it in LDS, out[2] LDS
+ * bytes a workgroup of the emit pass takes */
+void flbgpu_kubernetes_layout(flbgpu_filter *f, uint64_t out[3]);
+
 /* ---- filter_rewrite_tag: replaces cb_rewrite_tag_init / cb_rewrite_tag_filter / cb_rewrite_tag_exit ----
  * plugins/filter_rewrite_tag/rewrite_tag.c:112-190 (process_config, behind the config map of :590-613), 356-423 (process_record),
  * 425-557 (one call); src/flb_record_accessor.c:74-230 (the parts of an accessor), 456-619 (ra_translate_*), 644-699
