@@ -5,7 +5,7 @@
 // [out_off[r], out_off[r + 1]) through the bounded sink and no further.  ONE function, ex_record, writes a record into either sink,
 // so both passes walk the same code.  k_expect_table places one entry per failing row in record order from a scan over the fail flags.
 // Every loop is bounded by a length (never by a sentinel); nothing recurses.  Included inside namespace flbgpu after kdev.inc,
-// canon_walk.inc, ra_lds.inc and tc_sink.inc.
+// lane_rows.inc, canon_walk.inc and ra_lds.inc.
 
 struct ExTable {
     const LDS_AS uint32_t *w;       // the table's words in LDS
@@ -49,7 +49,7 @@ DEV uint32_t ex_rules(const ExTable &tb, const uint8_t *rec, const uint8_t *body
         default:
             // flb_sds_cmp: the lengths, then strncmp over them -- the expected text is a C string, so no NUL ends the walk early
             if (vt == EXT_NONE) how = EXF_NOT_FOUND;
-            else if (vt == EXT_STRING && (t.len != r[4] || !tc_eq(tb.w + (r[5] >> 2), r[4], t.next))) how = EXF_DIFFERENT;
+            else if (vt == EXT_STRING && (t.len != r[4] || !lds_eq(tb.w + (r[5] >> 2), r[4], t.next))) how = EXF_DIFFERENT;
             break;
         }
         if (!how) continue;
@@ -62,33 +62,14 @@ DEV uint32_t ex_rules(const ExTable &tb, const uint8_t *rec, const uint8_t *body
 // the rebuilt record (:498-532) into s: EventTime, the metadata re-packed, a map32 header for the body's entries and one more, the
 // result entry, the body's entries re-packed.  false: the row is not one well-formed event
 template <class S> DEV bool ex_record(const ExTable &tb, const Event &ev, const uint8_t *end, bool failed, S &s) {
-    s.put32(0x00d79292u);
-    s.put32(__builtin_bswap32((uint32_t) ev.sec));
-    s.put32(__builtin_bswap32((uint32_t) ev.nsec));
-    if (ev.meta) mp_canon(ev.meta, ev.meta_end, s); else s.put(0x80);
+    put_event_head(s, (uint32_t) ev.sec, (uint32_t) ev.nsec);
+    put_meta(s, ev);
     const Tok bm = mp_tok(ev.body, end);
     s.put(0xdf);
     pk_be(s, (uint64_t) bm.len + 1, 4);
-    tc_put_lds(s, tb.w + (tb.w[3] >> 2), tb.w[2]);
+    put_lds(s, tb.w + (tb.w[3] >> 2), tb.w[2]);
     s.put(failed ? 0xc2 : 0xc3);
-    const uint8_t *p = bm.next, *span = nullptr;
-    for (uint32_t i = 0; i < bm.len; i++) {
-        const uint8_t *e0 = p;
-        uint64_t es = 0;
-        bool canon = true;
-        const uint8_t *v = rm_walk(p, end, 2, es, canon);
-        if (!v) return false;
-        p = rm_walk(v, end, 2, es, canon);
-        if (!p) return false;
-        // runs of entries whose bytes already are the packer's go out as one span
-        if (canon) { if (!span) span = e0; continue; }
-        if (span) { tc_span(s, span, (uint64_t) (e0 - span)); span = nullptr; }
-        mp_canon(e0, end, s, 2);
-        mp_canon(v, end, s, 2);
-    }
-    if (p != end) return false;
-    if (span) tc_span(s, span, (uint64_t) (p - span));
-    return true;
+    return put_entries(s, bm, end, [](uint32_t, const uint8_t *, const uint8_t *) { return ENTRY_KEEP; });
 }
 
 struct ExRow {
@@ -125,9 +106,9 @@ template <int PASS> DEV ExRow ex_row(const ExpectArgs &a, const ExTable &tb, uin
 DEV bool ex_emit(const ExpectArgs &a, const ExTable &tb, uint64_t r) {
     const uint8_t *rec = a.data + a.row_off[r], *end = a.data + a.row_off[r + 1];
     uint8_t *o0 = a.out + a.out_off[r], *o1 = a.out + a.out_off[r + 1];
-    TcSink bs(o0, o1);
+    BoundedSink bs(o0, o1);
     const uint32_t vd = a.verdict[r];
-    if (vd & EXV_RAW) tc_span(bs, rec, (uint64_t) (end - rec));
+    if (vd & EXV_RAW) put_span(bs, rec, (uint64_t) (end - rec));
     else {
         const Event ev = decode_event(rec, end, false);
         if (ev.flags & RF_BAD) return false;
@@ -144,20 +125,14 @@ DEV bool ex_emit(const ExpectArgs &a, const ExTable &tb, uint64_t r) {
 #endif
 template <int PASS>
 __global__ void __attribute__((amdgpu_waves_per_eu(EX_WAVES, EX_WAVES))) __launch_bounds__(EX_BLOCK) k_expect(ExpectArgs a) {
-    LDS_AS uint32_t *lds = (LDS_AS uint32_t *) g_lds;
-    for (uint32_t i = threadIdx.x; i < a.table_bytes / 4; i += EX_BLOCK) lds[i] = a.table[i];
+    LDS_AS uint32_t *lds = lane_stage_table<EX_BLOCK>(a.table, a.table_bytes);
     __syncthreads();
     const ExTable tb{lds, lds[0]};
-    const uint64_t gsz = (uint64_t) gridDim.x * EX_BLOCK;
-    const uint32_t lane = threadIdx.x & 63u;
     unsigned long long n_chk = 0, n_fail = 0, n_out = 0, n_big = 0, n_mis = 0;
-    // every wave walks in step (the trip count is the wave's, not the lane's): the ballots below see whole waves
-    for (uint64_t r0 = (uint64_t) blockIdx.x * EX_BLOCK + (threadIdx.x & ~63u); r0 < a.n; r0 += gsz) {
-        const uint64_t r = r0 + lane;
-        const bool live = r < a.n;
+    lane_wave_rows<EX_BLOCK>(a.n, [&](uint64_t r, bool live) {
         if (PASS == EX_EMIT) {
             if (live && a.len[r] && !ex_emit(a, tb, r)) n_mis++;
-            continue;
+            return;
         }
         ExRow w;
         w.bad = false; w.verdict = 0; w.voff = 0; w.vlen = 0; w.len = 0;
@@ -172,24 +147,15 @@ __global__ void __attribute__((amdgpu_waves_per_eu(EX_WAVES, EX_WAVES))) __launc
             a.fail[r] = (w.verdict & EXV_FAILED) ? 1u : 0u;
             if (PASS == EX_SIZE) a.len[r] = (uint32_t) w.len;
         }
-        const unsigned long long b_chk = __ballot((w.verdict & EXV_CHECKED) != 0), b_fail = __ballot((w.verdict & EXV_FAILED) != 0),
-                                 b_out = __ballot(w.len != 0 && (w.verdict & EXV_CHECKED) != 0);      // (records, not markers)
-        if (lane == 0) {
-            n_chk += __popcll(b_chk); n_fail += __popcll(b_fail); n_out += __popcll(b_out);
-            // the first failing row: one atomic per wave that has one
-            if (b_fail) atomicMin(&a.firsts[1], (unsigned long long) (r0 + __ffsll((long long) b_fail) - 1));
-        }
-    }
-    if (PASS == EX_EMIT) {
-        if (n_mis) atomicAdd(&a.counts[4], n_mis);
-        return;
-    }
-    if (lane == 0) {
-        if (n_chk) atomicAdd(&a.counts[0], n_chk);
-        if (n_fail) atomicAdd(&a.counts[1], n_fail);
-        if (n_out) atomicAdd(&a.counts[2], n_out);
-    }
-    if (n_big) atomicAdd(&a.counts[3], n_big);
+        lane_count(n_chk, (w.verdict & EXV_CHECKED) != 0);
+        lane_count(n_out, w.len != 0 && (w.verdict & EXV_CHECKED) != 0);                                    // (records, not markers)
+        const unsigned long long b_fail = lane_count(n_fail, (w.verdict & EXV_FAILED) != 0);
+        // the first failing row (r is the wave's first row on lane 0): one atomic per wave that has one
+        if ((threadIdx.x & 63u) == 0 && b_fail) atomicMin(&a.firsts[1], (unsigned long long) (r + __ffsll((long long) b_fail) - 1));
+    });
+    if (PASS == EX_EMIT) { lane_flush(&a.counts[4], n_mis); return; }
+    lane_flush(&a.counts[0], n_chk); lane_flush(&a.counts[1], n_fail); lane_flush(&a.counts[2], n_out);      // (lane 0's: one atomic a wave)
+    lane_flush(&a.counts[3], n_big);
 }
 
 // the failure table: the entry of failing row r stands at fail_idx[r], so the table is in record order whatever the launch order was
@@ -210,14 +176,9 @@ __global__ void __launch_bounds__(EX_BLOCK) k_expect_table(ExpectArgs a) {
     }
 }
 
-static unsigned ex_blocks(uint64_t n) {
-    uint64_t blocks = (n + EX_BLOCK - 1) / EX_BLOCK;
-    return (unsigned) (blocks > 65536 ? 65536 : blocks);
-}
-
 void launch_expect(const ExpectArgs &a, int pass, hipStream_t st) {
     if (a.n == 0) return;
-    const dim3 g(ex_blocks(a.n)), b(EX_BLOCK);
+    const dim3 g(lane_blocks<EX_BLOCK>(a.n)), b(EX_BLOCK);
     if (pass == EX_EMIT) hipLaunchKernelGGL(k_expect<EX_EMIT>, g, b, a.table_bytes, st, a);
     else if (pass == EX_SIZE) hipLaunchKernelGGL(k_expect<EX_SIZE>, g, b, a.table_bytes, st, a);
     else hipLaunchKernelGGL(k_expect<EX_CHECK>, g, b, a.table_bytes, st, a);
@@ -225,5 +186,5 @@ void launch_expect(const ExpectArgs &a, int pass, hipStream_t st) {
 
 void launch_expect_table(const ExpectArgs &a, hipStream_t st) {
     if (a.n == 0) return;
-    hipLaunchKernelGGL(k_expect_table, dim3(ex_blocks(a.n)), dim3(EX_BLOCK), 0, st, a);
+    hipLaunchKernelGGL(k_expect_table, dim3(lane_blocks<EX_BLOCK>(a.n)), dim3(EX_BLOCK), 0, st, a);
 }

@@ -44,4 +44,18 @@ void set_out(flbgpu_filter *f, flbgpu_dev_chunk *out, uint64_t n, uint64_t total
     out->data = f->d_out.p; out->row_off = f->d_off.as<uint64_t>(); out->n = n; out->bytes = total;
 }
 
+// the most blocks a lane-per-record launch gets (lane_rows.inc): 65536.  The test switch FLBGPU_LANE_MAX_BLOCKS=<1 ... 65536>, read
+// once per process, lowers it, so that the row loops' further trips are met with a thousand records; anything else leaves 65536.
+unsigned lane_max_blocks() {
+    static const unsigned cap = [] {
+        const char *e = getenv("FLBGPU_LANE_MAX_BLOCKS");
+        char *end = nullptr;
+        const long v = e ? strtol(e, &end, 10) : 0;
+        return (e && end != e && *end == 0 && v >= 1 && v <= 65536) ? (unsigned) v : 65536u;
+    }();
+    return cap;
+}
+
 }  // namespace flbgpu
+
+extern "C" unsigned flbgpu_lane_max_blocks(void) { return flbgpu::lane_max_blocks(); }

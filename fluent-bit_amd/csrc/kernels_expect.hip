@@ -10,9 +10,9 @@
 namespace flbgpu {
 
 #include "kdev.inc"
+#include "lane_rows.inc"
 #include "canon_walk.inc"
 #include "ra_lds.inc"
-#include "tc_sink.inc"
 #include "expect_kernels.inc"
 
 }  // namespace flbgpu

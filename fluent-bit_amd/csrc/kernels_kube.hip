@@ -12,8 +12,8 @@
 namespace flbgpu {
 
 #include "kdev.inc"
+#include "lane_rows.inc"
 #include "canon_walk.inc"
-#include "tc_sink.inc"
 #include "kube_kernels.inc"
 
 }  // namespace flbgpu

@@ -10,6 +10,7 @@
 namespace flbgpu {
 
 #include "kdev.inc"
+#include "lane_rows.inc"
 #include "mlfilter_kernels.inc"
 
 }  // namespace flbgpu

@@ -10,6 +10,7 @@
 namespace flbgpu {
 
 #include "kdev.inc"
+#include "lane_rows.inc"
 #include "modify_kernels.inc"
 
 }  // namespace flbgpu

@@ -10,6 +10,7 @@
 namespace flbgpu {
 
 #include "kdev.inc"
+#include "lane_rows.inc"
 #include "canon_walk.inc"
 #include "nest_kernels.inc"
 

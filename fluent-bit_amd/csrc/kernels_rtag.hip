@@ -10,6 +10,7 @@
 namespace flbgpu {
 
 #include "kdev.inc"
+#include "lane_rows.inc"
 #include "ra_lds.inc"
 #include "fmt_dev.inc"
 #include "rtag_kernels.inc"

@@ -10,7 +10,7 @@
 // the tail behind each of its records with all 64 lanes (kb_append), out of LDS when the tail fits the budget, else out of HBM / L2.
 // The EXACT instantiation (wide bit stack, big-integer decimals) takes the rows the first one deferred, as pjson_kernels.inc does.
 // Every loop is bounded by a length (never by a sentinel); nothing recurses.  Included inside namespace flbgpu after kdev.inc,
-// canon_walk.inc and tc_sink.inc.
+// lane_rows.inc and canon_walk.inc.
 
 enum { KBM_UNSET = 0, KBM_NONE = 1, KBM_PARSED = 2, KBM_MAP = 3 };
 
@@ -154,53 +154,36 @@ struct KbRow {
 // one record into s (:318-584, without the tail).  false: the row is not one well-formed event
 template <bool EXACT, int NW, class S>
 DEV bool kb_record(const KbCfg &cf, const Event &ev, const uint8_t *end, uint32_t log_index, const KbMerge &m, const uint8_t *log_val, uint32_t log_len, S &s) {
-    s.put32(0x00d79292u);
-    s.put32(__builtin_bswap32((uint32_t) ev.sec));
-    s.put32(__builtin_bswap32((uint32_t) ev.nsec));
+    put_event_head(s, (uint32_t) ev.sec, (uint32_t) ev.nsec);
     // (the metadata is never set: the encoder's dynamic field closes as an empty map32, like the body's header)
     s.put(0xdf);
     s.put32(0);
     const bool keep_log = (cf.flags & KBF_KEEP_LOG) != 0, trim = (cf.flags & KBF_TRIM) != 0;
     const Tok bm = mp_tok(ev.body, end);
-    uint8_t *hdr = tc_open_hdr(s);
+    uint8_t *hdr = open_map32(s);
     uint64_t entries = 0;
-    const uint8_t *p = bm.next, *span = nullptr, *merged_map = nullptr;
-    for (uint32_t i = 0; i < bm.len; i++) {
-        const uint8_t *e0 = p;
-        uint64_t es = 0;
-        bool canon = true;
-        const uint8_t *v = rm_walk(p, end, 2, es, canon);
-        if (!v) return false;
-        p = rm_walk(v, end, 2, es, canon);
-        if (!p) return false;
+    const uint8_t *merged_map = nullptr;
+    const bool whole = put_entries(s, bm, end, [&](uint32_t i, const uint8_t *, const uint8_t *v) {
         if (i == log_index) {
-            if (span) { tc_span(s, span, (uint64_t) (e0 - span)); span = nullptr; }
             if (m.status == KBM_MAP) merged_map = v;
-            if (keep_log && (m.status == KBM_NONE || m.status == KBM_PARSED)) {
-                // the key as it is packed again, the value as a STR of the same bytes (:442-446)
-                mp_canon(e0, end, s, 2);
-                pk_str_hdr(s, log_len);
-                tc_span(s, log_val, log_len);
-                entries++;
-                continue;
-            }
-            if (!(keep_log || m.status == KBM_NONE)) continue;        // merged and keep_log off -- or a value of another type (:452)
+            if (keep_log && (m.status == KBM_NONE || m.status == KBM_PARSED)) { entries++; return ENTRY_OWN; }
+            if (!(keep_log || m.status == KBM_NONE)) return ENTRY_DROP;     // merged and keep_log off -- or a value of another type (:452)
         }
         entries++;
-        // runs of entries whose bytes already are the packer's go out as one span
-        if (canon) { if (!span) span = e0; continue; }
-        if (span) { tc_span(s, span, (uint64_t) (e0 - span)); span = nullptr; }
+        return ENTRY_KEEP;
+    }, [&](uint32_t, const uint8_t *e0, const uint8_t *) {
+        // `log` kept beside what it merged into: the key as it is packed again, the value as a STR of the same bytes (:442-446)
         mp_canon(e0, end, s, 2);
-        mp_canon(v, end, s, 2);
-    }
-    if (p != end) return false;
-    if (span) tc_span(s, span, (uint64_t) (p - span));
+        pk_str_hdr(s, log_len);
+        put_span(s, log_val, log_len);
+    });
+    if (!whole) return false;
     // the merged pairs, in place or under merge_log_key (:474-584): the key only when there is at least one entry
     uint64_t inner = 0;
     uint8_t *ihdr = nullptr;
     const bool nest = (cf.flags & KBF_MERGE_KEY) != 0;
     if (m.status == KBM_PARSED && !m.empty) {
-        if (nest) { tc_put_lds(s, cf.w + KB_HDR_WORDS, cf.key_bytes); ihdr = tc_open_hdr(s); }
+        if (nest) { put_lds(s, cf.w + KB_HDR_WORDS, cf.key_bytes); ihdr = open_map32(s); }
         JsonSrc js;
         js.p = log_val; js.len = log_len;
         uint32_t np = 0, mo = 0;
@@ -216,18 +199,18 @@ DEV bool kb_record(const KbCfg &cf, const Event &ev, const uint8_t *end, uint32_
     else if (m.status == KBM_MAP) {
         const Tok mt = mp_tok(merged_map, end);
         if (mt.len) {
-            if (nest) { tc_put_lds(s, cf.w + KB_HDR_WORDS, cf.key_bytes); ihdr = tc_open_hdr(s); }
+            if (nest) { put_lds(s, cf.w + KB_HDR_WORDS, cf.key_bytes); ihdr = open_map32(s); }
             const uint8_t *q = mt.next;
             for (uint32_t i = 0; i < 2 * mt.len; i++) { q = mp_canon(q, end, s, 3); if (!q) return false; }
             inner = mt.len;
         }
     }
     if (inner) {
-        if (nest) { tc_close_hdr(s, ihdr, inner); entries++; }
+        if (nest) { close_map32(s, ihdr, inner); entries++; }
         else entries += inner;
     }
     // (the tail's pairs -- kubernetes, kubernetes_namespace -- are part of the body)
-    tc_close_hdr(s, hdr, entries + ((cf.flags >> KBF_TAIL_PAIRS_SHIFT) & 3u));
+    close_map32(s, hdr, entries + ((cf.flags >> KBF_TAIL_PAIRS_SHIFT) & 3u));
     return true;
 }
 
@@ -313,21 +296,17 @@ template <class SRC> DEV void kb_append(uint8_t *dst, SRC src, uint32_t n, uint3
 template <int PASS, bool EXACT>
 __global__ void __launch_bounds__(KB_BLOCK) k_kube(KubeArgs a) {
     constexpr int NW = EXACT ? JSON_GENERIC_WORDS : 1;
-    LDS_AS uint32_t *lds = (LDS_AS uint32_t *) g_lds;
-    for (uint32_t i = threadIdx.x; i < a.table_bytes / 4; i += KB_BLOCK) lds[i] = a.table[i];
+    LDS_AS uint32_t *lds = lane_stage_table<KB_BLOCK>(a.table, a.table_bytes);
     LDS_AS uint8_t *tail_lds = (LDS_AS uint8_t *) g_lds + a.table_bytes;
     if (PASS == KB_EMIT && a.tail_in_lds) for (uint32_t i = threadIdx.x; i < a.tail_bytes; i += KB_BLOCK) tail_lds[i] = a.tail[i];
     __syncthreads();
     KbCfg cf;
     cf.w = lds; cf.flags = lds[0]; cf.key_bytes = lds[1]; cf.tail_bytes = a.tail_bytes;
     const uint32_t T = a.tail_bytes;
-    const uint64_t gsz = (uint64_t) gridDim.x * KB_BLOCK;
     const uint32_t lane = threadIdx.x & 63u;
     unsigned long long n_seen = 0, n_merged = 0, n_excl = 0, n_odd = 0, n_out = 0, n_big = 0, n_mis = 0, n_defer = 0;
-    // every wave walks in step (the trip count is the wave's, not the lane's): the ballots and the shuffles below see whole waves
-    for (uint64_t r0 = (uint64_t) blockIdx.x * KB_BLOCK + (threadIdx.x & ~63u); r0 < a.n; r0 += gsz) {
-        const uint64_t r = r0 + lane;
-        const bool live = r < a.n;
+    // (the tail's ballot and shuffles below need the whole wave in every trip)
+    lane_wave_rows<KB_BLOCK>(a.n, [&](uint64_t r, bool live) {
         uint8_t st = 0;
         if (live && (PASS == KB_EMIT || EXACT)) st = a.state[r];
         const bool mine = live && (EXACT ? (st & KBS_DEFER) != 0 : true);
@@ -339,7 +318,7 @@ __global__ void __launch_bounds__(KB_BLOCK) k_kube(KubeArgs a) {
             if (writes) {
                 uint8_t *o0 = a.out + a.out_off[r], *o1 = a.out + a.out_off[r + 1];
                 tail_at = a.out_off[r + 1] - T;
-                TcSink bs(o0, o1 - T);
+                BoundedSink bs(o0, o1 - T);
                 const KbRow w = kb_row<EXACT, NW, KB_EMIT>(cf, rec, end, bs, st);
                 if (w.bad || w.defer || bs.over || bs.p != o1 - T) n_mis++;
             }
@@ -352,12 +331,12 @@ __global__ void __launch_bounds__(KB_BLOCK) k_kube(KubeArgs a) {
                 if (a.tail_in_lds) kb_append<const LDS_AS uint8_t *>(dst, tail_lds, T, lane);
                 else kb_append<const uint8_t *>(dst, a.tail, T, lane);
             }
-            continue;
+            return;
         }
-        if (!mine) continue;
+        if (!mine) return;
         CountSink cs;
         KbRow w = kb_row<EXACT, NW, KB_SIZE>(cf, rec, end, cs);
-        if (w.defer) { a.state[r] = KBS_DEFER; a.len[r] = 0; n_defer++; continue; }      // (never under EXACT)
+        if (w.defer) { a.state[r] = KBS_DEFER; a.len[r] = 0; n_defer++; return; }        // (never under EXACT)
         uint64_t len = 0;
         if (w.bad) atomicMin(&a.firsts[0], (unsigned long long) r);
         else {
@@ -373,23 +352,10 @@ __global__ void __launch_bounds__(KB_BLOCK) k_kube(KubeArgs a) {
         }
         a.len[r] = (uint32_t) len;
         a.state[r] = (uint8_t) ((len ? KBS_OUT : 0) | (EXACT ? KBS_DEFER : 0) | w.sized);
-    }
-    if (PASS == KB_EMIT) {
-        if (n_mis) atomicAdd(&a.counts[6], n_mis);
-        return;
-    }
-    if (n_seen) atomicAdd(&a.counts[0], n_seen);
-    if (n_merged) atomicAdd(&a.counts[1], n_merged);
-    if (n_excl) atomicAdd(&a.counts[2], n_excl);
-    if (n_odd) atomicAdd(&a.counts[3], n_odd);
-    if (n_out) atomicAdd(&a.counts[4], n_out);
-    if (n_big) atomicAdd(&a.counts[5], n_big);
-    if (n_defer) atomicAdd(&a.counts[7], n_defer);
-}
-
-static unsigned kb_blocks(uint64_t n) {
-    uint64_t blocks = (n + KB_BLOCK - 1) / KB_BLOCK;
-    return (unsigned) (blocks > 65536 ? 65536 : blocks);
+    });
+    if (PASS == KB_EMIT) { lane_flush(&a.counts[6], n_mis); return; }
+    lane_flush(&a.counts[0], n_seen); lane_flush(&a.counts[1], n_merged); lane_flush(&a.counts[2], n_excl); lane_flush(&a.counts[3], n_odd);
+    lane_flush(&a.counts[4], n_out); lane_flush(&a.counts[5], n_big); lane_flush(&a.counts[7], n_defer);
 }
 
 void launch_kube(const KubeArgs &a, int pass, bool exact, hipStream_t st) {
@@ -401,7 +367,7 @@ void launch_kube(const KubeArgs &a, int pass, bool exact, hipStream_t st) {
         for (const void *k : ks) (void) hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
         attr_set = true;
     }
-    const dim3 g(kb_blocks(a.n)), b(KB_BLOCK);
+    const dim3 g(lane_blocks<KB_BLOCK>(a.n)), b(KB_BLOCK);
     const size_t lds = a.table_bytes + (a.tail_in_lds ? a.tail_bytes : 0);
     if (pass == KB_EMIT) {
         if (exact) hipLaunchKernelGGL((k_kube<KB_EMIT, true>), g, b, lds, st, a);

@@ -13,7 +13,7 @@
 //                 behind it -- an item whose rule flushes the group registers ITSELF into the emptied group (package_content :271-273)
 //   k_mlf_size    the first item of a group sizes the group's record, k_mlf_emit writes it: ONE function, mlf_record, behind a counting
 //                 sink and behind a sink bounded by the record's own room; every item copies its own text to its place
-// Included inside namespace flbgpu after kdev.inc.
+// Included inside namespace flbgpu after kdev.inc and lane_rows.inc.
 
 constexpr int MLF_BLOCK = 256;
 enum { MLF_ALONE = 0, MLF_START = 1, MLF_CONT = 2, MLF_APP = 3 };
@@ -187,11 +187,6 @@ template <class S> DEV bool mlf_record(S &s, const MlfArgs &a, uint64_t f, uint6
     return p == end;
 }
 
-DEV unsigned long long mlf_wave_sum(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ void __launch_bounds__(MLF_BLOCK) k_mlf_class(MlfArgs a) {
     unsigned long long n_meta = 0;
     for (uint64_t r = (uint64_t) blockIdx.x * MLF_BLOCK + threadIdx.x; r < a.n; r += (uint64_t) gridDim.x * MLF_BLOCK) {
@@ -207,7 +202,7 @@ __global__ void __launch_bounds__(MLF_BLOCK) k_mlf_class(MlfArgs a) {
         }
         a.keep[r] = keep;
     }
-    n_meta = mlf_wave_sum(n_meta);
+    n_meta = lane_wave_sum(n_meta);
     if ((threadIdx.x & 63u) == 0 && n_meta) atomicAdd(&a.w->meta_refused, n_meta);
 }
 
@@ -285,7 +280,7 @@ __global__ void __launch_bounds__(MLF_BLOCK) k_mlf_plan(MlfArgs a) {
         }
         a.ev[2 * k] = e0; a.ev[2 * k + 1] = e1;
     }
-    n_trunc = mlf_wave_sum(n_trunc); n_empty = mlf_wave_sum(n_empty);
+    n_trunc = lane_wave_sum(n_trunc); n_empty = lane_wave_sum(n_empty);
     if ((threadIdx.x & 63u) == 0) {
         if (n_trunc) atomicAdd(&a.w->truncated, n_trunc);
         if (n_empty) atomicAdd(&a.w->empty_start, n_empty);
@@ -330,7 +325,7 @@ __global__ void __launch_bounds__(MLF_BLOCK) k_mlf_size(MlfArgs a) {
         }
         a.plen[k] = plen; a.pre[k] = pre; a.dup[k] = dup; a.nrec[k] = nrec;
     }
-    n_big = mlf_wave_sum(n_big); n_mis = mlf_wave_sum(n_mis);
+    n_big = lane_wave_sum(n_big); n_mis = lane_wave_sum(n_mis);
     if ((threadIdx.x & 63u) == 0) {
         if (n_big) atomicAdd(&a.w->big, n_big);
         if (n_mis) atomicAdd(&a.w->mismatch, n_mis);
@@ -368,14 +363,12 @@ __global__ void __launch_bounds__(MLF_BLOCK) k_mlf_emit(MlfArgs a) {
             a.rows_out[a.ridx[k] + (k == f ? 1 : 0)] = (uint64_t) (d0 - a.out);
         }
     }
-    n_mis = mlf_wave_sum(n_mis);
+    n_mis = lane_wave_sum(n_mis);
     if ((threadIdx.x & 63u) == 0 && n_mis) atomicAdd(&a.w->mismatch, n_mis);
 }
 
-static unsigned mlf_blocks(uint64_t n) {
-    uint64_t b = (n + MLF_BLOCK - 1) / MLF_BLOCK;
-    return (unsigned) (b > 65536 ? 65536 : b ? b : 1);
-}
+// (a launch over no rows still runs one block: k_mlf_items writes the first item's columns)
+static unsigned mlf_blocks(uint64_t n) { return lane_blocks<MLF_BLOCK>(n ? n : 1); }
 void launch_mlf_class(const MlfArgs &a, hipStream_t st) { if (a.n) hipLaunchKernelGGL(k_mlf_class, dim3(mlf_blocks(a.n)), dim3(MLF_BLOCK), 0, st, a); }
 void launch_mlf_items(const MlfArgs &a, hipStream_t st) { hipLaunchKernelGGL(k_mlf_items, dim3(mlf_blocks(a.n)), dim3(MLF_BLOCK), 0, st, a); }
 void launch_mlf_fix(const MlfArgs &a, hipStream_t st) { hipLaunchKernelGGL(k_mlf_fix, dim3(mlf_blocks(a.N)), dim3(MLF_BLOCK), 0, st, a); }

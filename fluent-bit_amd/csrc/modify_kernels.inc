@@ -4,7 +4,7 @@
 // String and regex tests give the same answers on the original bytes as on msgpack_pack_object's re-pack: re-packing changes
 // headers, never STR / BIN payloads.  The one place where the re-packed bytes themselves matter is the prefix test's overread
 // (mod_key_prefix).  Two launches and a scan: the size pass writes every row's output length, the emit pass writes the rows.
-// Included inside namespace flbgpu after kdev.inc.
+// Included inside namespace flbgpu after kdev.inc and lane_rows.inc.
 
 DEV uint32_t me_koff(uint64_t e) { return (uint32_t) e; }
 DEV uint32_t me_kid(uint64_t e) { return (uint32_t) (e >> 32) & 0xFFu; }
@@ -377,8 +377,7 @@ __global__ void __launch_bounds__(MOD_BLOCK) k_modify(ModArgs a) {
 
 void launch_modify(const ModArgs &a, bool emit, hipStream_t st) {
     if (a.n == 0) return;
-    uint64_t blocks = (a.n + MOD_BLOCK - 1) / MOD_BLOCK;
-    if (blocks > 65536) blocks = 65536;
-    if (emit) hipLaunchKernelGGL(k_modify<true>, dim3((unsigned) blocks), dim3(MOD_BLOCK), 0, st, a);
-    else hipLaunchKernelGGL(k_modify<false>, dim3((unsigned) blocks), dim3(MOD_BLOCK), 0, st, a);
+    const dim3 g(lane_blocks<MOD_BLOCK>(a.n)), b(MOD_BLOCK);
+    if (emit) hipLaunchKernelGGL(k_modify<true>, g, b, 0, st, a);
+    else hipLaunchKernelGGL(k_modify<false>, g, b, 0, st, a);
 }

@@ -4,8 +4,8 @@
 // and whether the row goes out as its own bytes (no entry matched: emit_raw_record, :685-690) or is built again; the emit pass copies
 // a raw row as one span and builds the others in two walks -- what stays, then what is nested or lifted.  Matching is strncmp on
 // bytes (the table holds no NUL): a compare longer than the key takes the record's next bytes in, one that would need bytes past the
-// record fails and is counted (the convention of mod_key_prefix).  Included inside namespace flbgpu after kdev.inc and
-// canon_walk.inc (rm_walk, rm_copy, RM_MAP_HDR).
+// record fails and is counted (the convention of mod_key_prefix).  Included inside namespace flbgpu after kdev.inc,
+// lane_rows.inc and canon_walk.inc.
 
 struct NestTable {
     const LDS_AS uint32_t *w;       // the table's words in LDS
@@ -47,12 +47,6 @@ DEV bool nst_lifted(const NestTable &tb, const Tok &k, const Tok &v, const uint8
     return nst_cmp(tb.w + (tb.key_off >> 2), tb.key_len, k.next, end, ovr);
 }
 
-template <class S> DEV void nst_put_lds(S &s, const LDS_AS uint32_t *e, uint32_t L) {
-    for (uint32_t j = 0; j < L; j++) s.put((e[j >> 2] >> (8 * (j & 3))) & 0xffu);
-}
-DEV void nst_copy(CountSink &s, const uint8_t *, uint32_t len) { s.n += len; }
-DEV void nst_copy(ByteSink &s, const uint8_t *src, uint32_t len) { s.copy(src, len); }
-
 // the key of a nested or lifted entry (map_transform_and_pack_each_fn :243-279, pack_map :421-453, the helpers :177-216): as it is
 // without a prefix; with one always a STR, the prefix in front of it or cut off where the key starts with it.  undef: the reference
 // reads a string out of a key that is neither STR nor BIN, or cuts a prefix off a key that is shorter than the prefix.
@@ -63,8 +57,8 @@ DEV void nst_key(const NestTable &tb, const Tok &k, const uint8_t *kp, const uin
     const LDS_AS uint32_t *pe = tb.w + (tb.pfx_off >> 2);
     if (tb.pfx == NEST_PFX_ADD) {
         pk_str_hdr(s, tb.pfx_len + k.len);
-        nst_put_lds(s, pe, tb.pfx_len);
-        nst_copy(s, k.next, k.len);
+        put_lds(s, pe, tb.pfx_len);
+        put_span(s, k.next, k.len);
         return;
     }
     uint32_t cut = 0;
@@ -73,7 +67,7 @@ DEV void nst_key(const NestTable &tb, const Tok &k, const uint8_t *kp, const uin
         cut = tb.pfx_len;
     }
     pk_str_hdr(s, k.len - cut);
-    nst_copy(s, k.next + cut, k.len - cut);
+    put_span(s, k.next + cut, k.len - cut);
 }
 
 struct NestRow {
@@ -82,10 +76,6 @@ struct NestRow {
     uint64_t len;                       // output bytes (0: nothing emitted)
 };
 
-DEV bool nst_time_ok(const Event &ev) {
-    return ev.sec >= 0 && (uint64_t) ev.sec <= 0xffffffffull && ev.nsec >= 0 && ev.nsec < 1000000000LL;
-}
-
 // the entries of a lifted map at p (n of them), each key through nst_key, each value re-packed; nullptr: malformed
 template <class S>
 DEV const uint8_t *nst_inner(const NestTable &tb, const uint8_t *p, const uint8_t *end, uint32_t n, S &s, uint32_t &ovr, bool &undef) {
@@ -93,7 +83,7 @@ DEV const uint8_t *nst_inner(const NestTable &tb, const uint8_t *p, const uint8_
         Tok k = mp_tok(p, end);
         uint64_t cs = 0;
         bool canon = true;
-        const uint8_t *v = rm_walk(p, end, 3, cs, canon);
+        const uint8_t *v = canon_walk(p, end, 3, cs, canon);
         if (!v) return nullptr;
         nst_key(tb, k, p, end, 3, s, ovr, undef);
         p = mp_canon(v, end, s, 3);
@@ -112,7 +102,8 @@ DEV NestRow nst_size(const NestArgs &a, const NestTable &tb, uint64_t r) {
     if (ev.flags & RF_BAD) { w.bad = true; return w; }
     // a record the rules would change is lost when the encoder refuses its time (set_timestamp, :506-511, :561-566) or, for nest,
     // the NULL key (:582-587): begin_record was called, nothing is committed and nothing goes out raw
-    const bool lost = !nst_time_ok(ev) || (tb.op == NEST_OP_NEST && !tb.has_key);
+    uint32_t sec, nsec;
+    const bool lost = !event_time_or_zero(ev, sec, nsec) || (tb.op == NEST_OP_NEST && !tb.has_key);
     Tok bm = mp_tok(ev.body, end);
     CountSink moved;                                                  // the nested / lifted entries as they go out
     uint64_t stay = 0, nmatch = 0;
@@ -123,10 +114,10 @@ DEV NestRow nst_size(const NestArgs &a, const NestTable &tb, uint64_t r) {
         Tok k = mp_tok(p, end);
         uint64_t ks = 0, vs = 0;
         bool canon = true;
-        const uint8_t *v = rm_walk(p, end, 2, ks, canon);
+        const uint8_t *v = canon_walk(p, end, 2, ks, canon);
         if (!v) { w.bad = true; return w; }
         if (tb.op == NEST_OP_NEST) {
-            const uint8_t *q = rm_walk(v, end, 2, vs, canon);
+            const uint8_t *q = canon_walk(v, end, 2, vs, canon);
             if (!q) { w.bad = true; return w; }
             if (nst_wild(tb, k, end, ovr)) {
                 nmatch++;
@@ -143,7 +134,7 @@ DEV NestRow nst_size(const NestArgs &a, const NestTable &tb, uint64_t r) {
                 if (!p) { w.bad = true; return w; }
             }
             else {
-                p = rm_walk(v, end, 2, vs, canon);
+                p = canon_walk(v, end, 2, vs, canon);
                 if (!p) { w.bad = true; return w; }
                 stay += ks + vs;
             }
@@ -157,19 +148,13 @@ DEV NestRow nst_size(const NestArgs &a, const NestTable &tb, uint64_t r) {
     if (lost) return w;
     if (undef) { w.undef = true; w.mode = NEST_ROW_RAW; w.len = (uint64_t) (end - rec); return w; }
     CountSink cs;
-    cs.n = 12 + RM_MAP_HDR;
-    if (ev.meta) mp_canon(ev.meta, ev.meta_end, cs); else cs.n += 1;
-    if (tb.op == NEST_OP_NEST) { pk_str_hdr(cs, tb.key_len); cs.n += tb.key_len + RM_MAP_HDR; }
+    cs.n = 12 + MAP32_HDR;
+    put_meta(cs, ev);
+    if (tb.op == NEST_OP_NEST) { pk_str_hdr(cs, tb.key_len); cs.n += tb.key_len + MAP32_HDR; }
     w.built = true;
     w.mode = NEST_ROW_BUILT;
     w.len = cs.n + stay + moved.n;
     return w;
-}
-
-DEV void nst_map32(uint8_t *at, uint64_t n) {
-    ByteSink hs(at);
-    hs.put(0xdf);
-    hs.put32(__builtin_bswap32((uint32_t) n));
 }
 
 // emit pass: a row the size pass marked as built again
@@ -177,16 +162,14 @@ DEV void nst_emit(const NestArgs &a, const NestTable &tb, uint64_t r) {
     const uint8_t *rec = a.data + a.row_off[r], *end = a.data + a.row_off[r + 1];
     Event ev = decode_event(rec, end, true);
     ByteSink bs(a.out + a.out_off[r]);
-    bs.put32(0x00d79292u);
-    bs.put32(__builtin_bswap32((uint32_t) ev.sec));
-    bs.put32(__builtin_bswap32((uint32_t) ev.nsec));
-    if (ev.meta) mp_canon(ev.meta, ev.meta_end, bs); else bs.put(0x80);
-    uint8_t *hdr = bs.p;                                              // the count is known when the walk is done
-    bs.p += RM_MAP_HDR;
+    put_event_head(bs, (uint32_t) ev.sec, (uint32_t) ev.nsec);
+    put_meta(bs, ev);
+    uint8_t *hdr = open_map32(bs);                                    // the count is known when the walk is done
     Tok bm = mp_tok(ev.body, end);
     uint32_t ovr = 0;
     bool undef = false;
-    // what stays, in order: runs of entries whose encoding is already canonical go out as one span
+    // what stays, in order: runs of entries whose encoding is already canonical go out as one span.  put_entries' walk without its
+    // checks (the size pass made them): with them nst_emit measured about 1 % slower on lifted maps (DESIGN 4n)
     const uint8_t *p = bm.next, *span = nullptr;
     uint64_t kept = 0, nmatch = 0;
     for (uint32_t i = 0; i < bm.len; i++) {
@@ -194,23 +177,22 @@ DEV void nst_emit(const NestArgs &a, const NestTable &tb, uint64_t r) {
         Tok k = mp_tok(p, end);
         uint64_t es = 0;
         bool canon = true;
-        const uint8_t *v = rm_walk(p, end, 2, es, canon);
-        p = rm_walk(v, end, 2, es, canon);
+        const uint8_t *v = canon_walk(p, end, 2, es, canon);
+        p = canon_walk(v, end, 2, es, canon);
         const bool hit = tb.op == NEST_OP_NEST ? nst_wild(tb, k, end, ovr) : nst_lifted(tb, k, mp_tok(v, end), end);
         nmatch += hit ? 1u : 0u;
         kept += hit ? 0u : 1u;
         if (!hit && canon) { if (!span) span = e0; continue; }
-        if (span) { rm_copy(bs, span, (uint64_t) (e0 - span)); span = nullptr; }
+        if (span) { put_span(bs, span, (uint64_t) (e0 - span)); span = nullptr; }
         if (!hit) { mp_canon(e0, end, bs, 2); mp_canon(v, end, bs, 2); }
     }
-    if (span) rm_copy(bs, span, (uint64_t) (p - span));
+    if (span) put_span(bs, span, (uint64_t) (p - span));
     uint64_t lifted = 0;
     if (tb.op == NEST_OP_NEST) {
         // the key as a STR and the nested map; the encoder's scopes always write map32 (src/flb_mp.c:591-603)
         pk_str_hdr(bs, tb.key_len);
-        nst_put_lds(bs, tb.w + (tb.key_off >> 2), tb.key_len);
-        nst_map32(bs.p, nmatch);
-        bs.p += RM_MAP_HDR;
+        put_lds(bs, tb.w + (tb.key_off >> 2), tb.key_len);
+        close_map32(bs, open_map32(bs), nmatch);
     }
     p = bm.next;
     for (uint32_t i = 0; i < bm.len && nmatch > 0; i++) {
@@ -235,31 +217,24 @@ DEV void nst_emit(const NestArgs &a, const NestTable &tb, uint64_t r) {
             else p = mp_skip(v, end, 2);
         }
     }
-    nst_map32(hdr, kept + (tb.op == NEST_OP_NEST ? 1u : lifted));
+    close_map32(bs, hdr, kept + (tb.op == NEST_OP_NEST ? 1u : lifted));
 }
 
 template <bool EMIT>
 __global__ void __launch_bounds__(NEST_BLOCK) k_nest(NestArgs a) {
-    LDS_AS uint32_t *lds = (LDS_AS uint32_t *) g_lds;
-    for (uint32_t i = threadIdx.x; i < a.table_bytes / 4; i += NEST_BLOCK) lds[i] = a.table[i];
+    NestTable tb{lane_stage_table<NEST_BLOCK>(a.table, a.table_bytes), a.op, a.nwild, a.pfx, a.has_key != 0, a.key_off, a.key_len, a.pfx_off, a.pfx_len};
     __syncthreads();
-    NestTable tb{lds, a.op, a.nwild, a.pfx, a.has_key != 0, a.key_off, a.key_len, a.pfx_off, a.pfx_len};
-    const uint64_t gsz = (uint64_t) gridDim.x * NEST_BLOCK;
-    const uint32_t lane = threadIdx.x & 63u;
     unsigned long long n_dec = 0, n_out = 0, n_built = 0, n_undef = 0, n_big = 0, n_ovr = 0;
-    // every wave walks in step (the trip count is the wave's, not the lane's): the ballots below see whole waves
-    for (uint64_t r0 = (uint64_t) blockIdx.x * NEST_BLOCK + (threadIdx.x & ~63u); r0 < a.n; r0 += gsz) {
-        const uint64_t r = r0 + lane;
-        const bool live = r < a.n;
+    lane_wave_rows<NEST_BLOCK>(a.n, [&](uint64_t r, bool live) {
         if (EMIT) {
             if (live && a.len[r]) {
                 if (a.mode[r] == NEST_ROW_BUILT) nst_emit(a, tb, r);
                 else {
                     ByteSink bs(a.out + a.out_off[r]);
-                    rm_copy(bs, a.data + a.row_off[r], a.row_off[r + 1] - a.row_off[r]);
+                    put_span(bs, a.data + a.row_off[r], a.row_off[r + 1] - a.row_off[r]);
                 }
             }
-            continue;
+            return;
         }
         NestRow w;
         w.bad = false; w.decoded = false; w.built = false; w.undef = false; w.mode = NEST_ROW_NONE; w.ovr = 0; w.len = 0;
@@ -272,27 +247,17 @@ __global__ void __launch_bounds__(NEST_BLOCK) k_nest(NestArgs a) {
             n_ovr += w.ovr;
             if (w.bad) atomicMin(a.first_bad, (unsigned long long) r);
         }
-        // the call-level facts of a wave's 64 records: counted by one lane from the ballots
-        const unsigned long long b_dec = __ballot(w.decoded), b_out = __ballot(w.len != 0), b_built = __ballot(w.built), b_undef = __ballot(w.undef);
-        if (lane == 0) { n_dec += __popcll(b_dec); n_out += __popcll(b_out); n_built += __popcll(b_built); n_undef += __popcll(b_undef); }
-    }
-    if (!EMIT) {
-        // one atomic per wave and counter that is not zero
-        if (lane == 0) {
-            if (n_dec) atomicAdd(&a.counts[0], n_dec);
-            if (n_out) atomicAdd(&a.counts[1], n_out);
-            if (n_built) atomicAdd(&a.counts[2], n_built);
-            if (n_undef) atomicAdd(&a.counts[5], n_undef);
-        }
-        if (n_big) atomicAdd(&a.counts[3], n_big);
-        if (n_ovr) atomicAdd(&a.counts[4], n_ovr);
-    }
+        lane_count(n_dec, w.decoded); lane_count(n_out, w.len != 0); lane_count(n_built, w.built); lane_count(n_undef, w.undef);
+    });
+    if (EMIT) return;
+    lane_flush(&a.counts[0], n_dec); lane_flush(&a.counts[1], n_out); lane_flush(&a.counts[2], n_built);      // (lane 0's: one atomic a wave)
+    lane_flush(&a.counts[5], n_undef);
+    lane_flush(&a.counts[3], n_big); lane_flush(&a.counts[4], n_ovr);
 }
 
 void launch_nest(const NestArgs &a, bool emit, hipStream_t st) {
     if (a.n == 0) return;
-    uint64_t blocks = (a.n + NEST_BLOCK - 1) / NEST_BLOCK;
-    if (blocks > 65536) blocks = 65536;
-    if (emit) hipLaunchKernelGGL(k_nest<true>, dim3((unsigned) blocks), dim3(NEST_BLOCK), a.table_bytes, st, a);
-    else hipLaunchKernelGGL(k_nest<false>, dim3((unsigned) blocks), dim3(NEST_BLOCK), a.table_bytes, st, a);
+    const dim3 g(lane_blocks<NEST_BLOCK>(a.n)), b(NEST_BLOCK);
+    if (emit) hipLaunchKernelGGL(k_nest<true>, g, b, a.table_bytes, st, a);
+    else hipLaunchKernelGGL(k_nest<false>, g, b, a.table_bytes, st, a);
 }

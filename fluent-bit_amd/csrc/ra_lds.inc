@@ -7,7 +7,7 @@ constexpr uint32_t RA_LDS_SUB_INDEX = 0x80000000u;
 
 // are the L bytes at key (all of them inside the record: mp_tok checked the payload) the entry at e?  A 4-byte load is issued
 // only where 4 bytes remain inside the key.
-DEV bool tc_eq(const LDS_AS uint32_t *e, uint32_t L, const uint8_t *key) {
+DEV bool lds_eq(const LDS_AS uint32_t *e, uint32_t L, const uint8_t *key) {
     uint32_t j = 0;
     bool eq = true;
     for (; eq && j + 4 <= L; j += 4) eq = ldu32(key + j) == e[j >> 2];
@@ -16,7 +16,7 @@ DEV bool tc_eq(const LDS_AS uint32_t *e, uint32_t L, const uint8_t *key) {
 }
 
 // ra_key_val_id (src/flb_ra_key.c:108-135): the value of the LAST entry of the map at `map` whose key is a STR equal to the name
-DEV const uint8_t *tc_find_last(const uint8_t *map, const uint8_t *end, const LDS_AS uint32_t *name, uint32_t nlen) {
+DEV const uint8_t *ra_lds_find_last(const uint8_t *map, const uint8_t *end, const LDS_AS uint32_t *name, uint32_t nlen) {
     Tok m = mp_tok(map, end);
     if (m.type != T_MAP) return nullptr;
     const uint8_t *p = m.next, *found = nullptr;
@@ -24,7 +24,7 @@ DEV const uint8_t *tc_find_last(const uint8_t *map, const uint8_t *end, const LD
         Tok k = mp_tok(p, end);
         const uint8_t *v = mp_end_of(k, p, end, 2);
         if (!v) return nullptr;
-        if (k.type == T_STR && k.len == nlen && tc_eq(name, nlen, k.next)) found = v;
+        if (k.type == T_STR && k.len == nlen && lds_eq(name, nlen, k.next)) found = v;
         p = mp_end_of(mp_tok(v, end), v, end, 2);
         if (!p) return nullptr;
     }
@@ -36,7 +36,7 @@ DEV const uint8_t *tc_find_last(const uint8_t *map, const uint8_t *end, const LD
 // array index is a value (subkey_to_object answers it with no key object, which only flb_ra_get_kv_pair's callers refuse).
 DEV const uint8_t *ra_lds_path(const LDS_AS uint32_t *tbl, const LDS_AS uint32_t *name, uint32_t nlen, const LDS_AS uint32_t *sub, uint32_t nsub,
                                const uint8_t *body, const uint8_t *end, bool index_ok) {
-    const uint8_t *val = tc_find_last(body, end, name, nlen);
+    const uint8_t *val = ra_lds_find_last(body, end, name, nlen);
     if (!val) return nullptr;
     Tok t = mp_tok(val, end);
     if ((t.type != T_MAP && t.type != T_ARRAY) || nsub == 0) return val;
@@ -57,7 +57,7 @@ DEV const uint8_t *ra_lds_path(const LDS_AS uint32_t *tbl, const LDS_AS uint32_t
             continue;
         }
         if (c.type != T_MAP) break;
-        const uint8_t *v = tc_find_last(cur, end, tbl + (sub[2 * s + 1] >> 2), s0);
+        const uint8_t *v = ra_lds_find_last(cur, end, tbl + (sub[2 * s + 1] >> 2), s0);
         if (!v) continue;                          // "try next entry": the levels are never completed
         cur = v;
         last_index = false;

@@ -3,8 +3,8 @@
 // canonical size of what stays; the body's order never changes and nothing is inserted between entries, so no entry list is kept.
 // Two launches around the shared scan: the size pass writes every row's output length, the emit pass walks the body
 // again, decides again (the table is in LDS, the key bytes are in the cache lines it copies anyway) and copies runs of adjacent kept
-// entries whose encoding is already canonical as one span.  Included inside namespace flbgpu after kdev.inc and
-// canon_walk.inc (rm_walk, RM_MAP_HDR, rm_copy).
+// entries whose encoding is already canonical as one span.  Included inside namespace flbgpu after kdev.inc,
+// lane_rows.inc and canon_walk.inc.
 
 struct RmTable {
     const LDS_AS uint32_t *w;       // the table's words in LDS
@@ -55,14 +55,6 @@ struct RmRow {
     uint64_t len;                       // output bytes (0: nothing emitted)
 };
 
-// the time the encoder writes: flb_log_event_encoder_set_timestamp refuses a time outside the EventTime range, its answer is
-// overwritten (:414-417) and the record goes out with the zero time begin_record left
-DEV void rm_time(const Event &ev, uint32_t &sec, uint32_t &nsec) {
-    const bool ok = ev.sec >= 0 && (uint64_t) ev.sec <= 0xffffffffull && ev.nsec >= 0 && ev.nsec < 1000000000LL;
-    sec = ok ? (uint32_t) ev.sec : 0;
-    nsec = ok ? (uint32_t) ev.nsec : 0;
-}
-
 // size pass: one record of cb_modifier_filter's loop (:351-463)
 DEV RmRow rm_size(const RecmodArgs &a, const RmTable &tb, uint64_t r) {
     RmRow w;
@@ -79,8 +71,8 @@ DEV RmRow rm_size(const RecmodArgs &a, const RmTable &tb, uint64_t r) {
     for (uint32_t i = 0; i < bm.len; i++) {
         Tok k = mp_tok(p, end);
         uint64_t es = 0;
-        p = rm_walk(p, end, 2, es, canon);
-        if (p) p = rm_walk(p, end, 2, es, canon);
+        p = canon_walk(p, end, 2, es, canon);
+        if (p) p = canon_walk(p, end, 2, es, canon);
         if (!p) { w.bad = true; return w; }
         if (!rm_removed(tb, k)) { kept++; size += es; }
     }
@@ -91,8 +83,8 @@ DEV RmRow rm_size(const RecmodArgs &a, const RmTable &tb, uint64_t r) {
     w.lost = kept != bm.len;
     if (kept + a.nrec == 0) return w;                                 // (:408-410)
     CountSink cs;
-    cs.n = 12 + RM_MAP_HDR;
-    if (ev.meta) mp_canon(ev.meta, ev.meta_end, cs); else cs.n += 1;
+    cs.n = 12 + MAP32_HDR;
+    put_meta(cs, ev);
     w.len = cs.n + size + a.tail_len;
     return w;
 }
@@ -103,13 +95,11 @@ DEV void rm_emit(const RecmodArgs &a, const RmTable &tb, uint64_t r) {
     Event ev = decode_event(rec, end, true);
     ByteSink bs(a.out + a.out_off[r]);
     uint32_t sec, nsec;
-    rm_time(ev, sec, nsec);
-    bs.put32(0x00d79292u);
-    bs.put32(__builtin_bswap32(sec));
-    bs.put32(__builtin_bswap32(nsec));
-    if (ev.meta) mp_canon(ev.meta, ev.meta_end, bs); else bs.put(0x80);
-    uint8_t *hdr = bs.p;                                              // the count is known when the walk is done
-    bs.p += RM_MAP_HDR;
+    event_time_or_zero(ev, sec, nsec);                                // (its answer is overwritten, :414-417)
+    put_event_head(bs, sec, nsec);
+    put_meta(bs, ev);
+    uint8_t *hdr = open_map32(bs);                                    // the count is known when the walk is done
+    // put_entries' walk without its checks (the size pass made them): with them this kernel measured 1 to 2 % slower (DESIGN 4n)
     Tok bm = mp_tok(ev.body, end);
     const uint8_t *p = bm.next, *span = nullptr;
     uint32_t kept = 0;
@@ -118,33 +108,29 @@ DEV void rm_emit(const RecmodArgs &a, const RmTable &tb, uint64_t r) {
         Tok k = mp_tok(p, end);
         uint64_t es = 0;
         bool canon = true;
-        const uint8_t *v = rm_walk(p, end, 2, es, canon);
-        p = rm_walk(v, end, 2, es, canon);
+        const uint8_t *v = canon_walk(p, end, 2, es, canon);
+        p = canon_walk(v, end, 2, es, canon);
         const bool keep = !rm_removed(tb, k);
         kept += keep ? 1u : 0u;
         if (keep && canon) { if (!span) span = e0; continue; }
-        if (span) { rm_copy(bs, span, (uint64_t) (e0 - span)); span = nullptr; }
+        if (span) { put_span(bs, span, (uint64_t) (e0 - span)); span = nullptr; }
         if (keep) { mp_canon(e0, end, bs, 2); mp_canon(v, end, bs, 2); }
     }
-    if (span) rm_copy(bs, span, (uint64_t) (p - span));
+    if (span) put_span(bs, span, (uint64_t) (p - span));
     if (a.tail_len) bs.copy(a.tail, a.tail_len);
-    ByteSink hs(hdr);
-    hs.put(0xdf);
-    hs.put32(__builtin_bswap32(kept + a.nrec));
+    close_map32(bs, hdr, kept + a.nrec);
 }
 
 template <bool EMIT>
 __global__ void __launch_bounds__(RECMOD_BLOCK) k_recmod(RecmodArgs a) {
-    LDS_AS uint32_t *lds = (LDS_AS uint32_t *) g_lds;
-    for (uint32_t i = threadIdx.x; i < a.table_bytes / 4; i += RECMOD_BLOCK) lds[i] = a.table[i];
+    RmTable tb{lane_stage_table<RECMOD_BLOCK>(a.table, a.table_bytes), a.nkeys, a.list};
     __syncthreads();
-    RmTable tb{lds, a.nkeys, a.list};
     const uint64_t gsz = (uint64_t) gridDim.x * RECMOD_BLOCK;
-    const uint32_t lane = threadIdx.x & 63u;
     unsigned long long n_dec = 0, n_out = 0, n_lost = 0, n_big = 0;
-    // every wave walks in step (the trip count is the wave's, not the lane's): the ballots below see whole waves
+    // lane_wave_rows' loop, written out: through the helper's lambda the emit pass measured 1 to 2 % slower on nest-shaped records
+    // (DESIGN 4n).  Every wave walks in step (the trip count is the wave's, not the lane's): lane_count's ballots see whole waves.
     for (uint64_t r0 = (uint64_t) blockIdx.x * RECMOD_BLOCK + (threadIdx.x & ~63u); r0 < a.n; r0 += gsz) {
-        const uint64_t r = r0 + lane;
+        const uint64_t r = r0 + (threadIdx.x & 63u);
         const bool live = r < a.n;
         if (EMIT) {
             if (live && a.len[r]) rm_emit(a, tb, r);
@@ -160,25 +146,16 @@ __global__ void __launch_bounds__(RECMOD_BLOCK) k_recmod(RecmodArgs a) {
             if (w.bad) atomicMin(a.first_bad, (unsigned long long) r);
             if (w.wide) atomicMin(a.first_wide, (unsigned long long) r);
         }
-        // the call-level facts of a wave's 64 records: counted by one lane from the ballots
-        const unsigned long long b_dec = __ballot(w.decoded), b_out = __ballot(w.len != 0), b_lost = __ballot(w.lost);
-        if (lane == 0) { n_dec += __popcll(b_dec); n_out += __popcll(b_out); n_lost += __popcll(b_lost); }
+        lane_count(n_dec, w.decoded); lane_count(n_out, w.len != 0); lane_count(n_lost, w.lost);
     }
-    if (!EMIT) {
-        // one atomic per wave and counter that is not zero
-        if (lane == 0) {
-            if (n_dec) atomicAdd(&a.counts[0], n_dec);
-            if (n_out) atomicAdd(&a.counts[1], n_out);
-            if (n_lost) atomicAdd(&a.counts[2], n_lost);
-        }
-        if (n_big) atomicAdd(&a.counts[3], n_big);
-    }
+    if (EMIT) return;
+    lane_flush(&a.counts[0], n_dec); lane_flush(&a.counts[1], n_out); lane_flush(&a.counts[2], n_lost);       // (lane 0's: one atomic a wave)
+    lane_flush(&a.counts[3], n_big);
 }
 
 void launch_recmod(const RecmodArgs &a, bool emit, hipStream_t st) {
     if (a.n == 0) return;
-    uint64_t blocks = (a.n + RECMOD_BLOCK - 1) / RECMOD_BLOCK;
-    if (blocks > 65536) blocks = 65536;
-    if (emit) hipLaunchKernelGGL(k_recmod<true>, dim3((unsigned) blocks), dim3(RECMOD_BLOCK), a.table_bytes, st, a);
-    else hipLaunchKernelGGL(k_recmod<false>, dim3((unsigned) blocks), dim3(RECMOD_BLOCK), a.table_bytes, st, a);
+    const dim3 g(lane_blocks<RECMOD_BLOCK>(a.n)), b(RECMOD_BLOCK);
+    if (emit) hipLaunchKernelGGL(k_recmod<true>, g, b, a.table_bytes, st, a);
+    else hipLaunchKernelGGL(k_recmod<false>, g, b, a.table_bytes, st, a);
 }

@@ -9,7 +9,7 @@
 // ONE function, rt_compose, writes a tag into whatever sink it is given: k_rtag<false> hands it a CountSink, k_rtag<true> an RtSink that
 // never stores outside [tag_off[r], tag_off[r + 1]).  A row whose written length is not its sized length is counted, not written past.
 // The kept records are copied by k_gather (kernels.hip), as filter_grep's are: emit_raw_record copies the record as it is.
-// Included inside namespace flbgpu after kdev.inc, ra_lds.inc and fmt_dev.inc.
+// Included inside namespace flbgpu after kdev.inc, lane_rows.inc, ra_lds.inc and fmt_dev.inc.
 
 struct RtTable {
     const LDS_AS uint32_t *w;       // the table's words in LDS
@@ -196,16 +196,9 @@ DEV void rt_compose(const RtagArgs &a, const RtTable &tb, uint32_t ri, const uin
     }
 }
 
-DEV unsigned long long rt_wave_sum(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ void __launch_bounds__(RT_BLOCK) k_rtag_match(RtagArgs a) {
-    LDS_AS uint32_t *lds = (LDS_AS uint32_t *) g_lds;
-    for (uint32_t i = threadIdx.x; i < a.table_bytes / 4; i += RT_BLOCK) lds[i] = a.table[i];
+    RtTable tb{lane_stage_table<RT_BLOCK>(a.table, a.table_bytes), a.nrules};
     __syncthreads();
-    RtTable tb{lds, a.nrules};
     const uint64_t gsz = (uint64_t) gridDim.x * RT_BLOCK;
     unsigned long long n_dec = 0, n_keep = 0, n_match = 0, n_big = 0;
     for (uint64_t r = (uint64_t) blockIdx.x * RT_BLOCK + threadIdx.x; r < a.n; r += gsz) {
@@ -232,7 +225,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_rtag_match(RtagArgs a) {
         }
         a.rule[r] = rule; a.keep_len[r] = keep; a.emit[r] = emit;
     }
-    n_dec = rt_wave_sum(n_dec); n_keep = rt_wave_sum(n_keep); n_match = rt_wave_sum(n_match); n_big = rt_wave_sum(n_big);
+    n_dec = lane_wave_sum(n_dec); n_keep = lane_wave_sum(n_keep); n_match = lane_wave_sum(n_match); n_big = lane_wave_sum(n_big);
     if ((threadIdx.x & 63u) == 0) {
         if (n_dec) atomicAdd(&a.counts[0], n_dec);
         if (n_keep) atomicAdd(&a.counts[1], n_keep);
@@ -245,10 +238,8 @@ __global__ void __launch_bounds__(RT_BLOCK) k_rtag_match(RtagArgs a) {
 // entry of the emitted table.  A wave keeps its own part of the capture scratch for the whole launch.
 template <bool EMIT>
 __global__ void __launch_bounds__(RT_BLOCK) k_rtag(RtagArgs a) {
-    LDS_AS uint32_t *lds = (LDS_AS uint32_t *) g_lds;
-    for (uint32_t i = threadIdx.x; i < a.table_bytes / 4; i += RT_BLOCK) lds[i] = a.table[i];
+    RtTable tb{lane_stage_table<RT_BLOCK>(a.table, a.table_bytes), a.nrules};
     __syncthreads();
-    RtTable tb{lds, a.nrules};
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t wave_slot = ((uint64_t) blockIdx.x * RT_BLOCK + threadIdx.x) >> 6;
     const uint64_t nwaves = ((uint64_t) gridDim.x * RT_BLOCK) >> 6;
@@ -311,7 +302,7 @@ __global__ void __launch_bounds__(RT_BLOCK) k_rtag(RtagArgs a) {
         a.table_out[e] = o;
     }
     // one atomic per wave and counter that is not zero (every lane of the wave is here again behind the loop)
-    n_mis = rt_wave_sum(n_mis); n_big = rt_wave_sum(n_big); n_bytes = rt_wave_sum(n_bytes);
+    n_mis = lane_wave_sum(n_mis); n_big = lane_wave_sum(n_big); n_bytes = lane_wave_sum(n_bytes);
     if (lane == 0) {
         if (n_mis) atomicAdd(&a.counts[4], n_mis);
         if (n_big) atomicAdd(&a.counts[3], n_big);
@@ -329,20 +320,15 @@ __global__ void __launch_bounds__(RT_BLOCK) k_rtag_refuse(RtagArgs a, const uint
     }
 }
 
-static unsigned rt_blocks(uint64_t n) {
-    uint64_t blocks = (n + RT_BLOCK - 1) / RT_BLOCK;
-    return (unsigned) (blocks > 65536 ? 65536 : blocks);
-}
-
 void launch_rtag_match(const RtagArgs &a, hipStream_t st) {
     if (a.n == 0) return;
-    hipLaunchKernelGGL(k_rtag_match, dim3(rt_blocks(a.n)), dim3(RT_BLOCK), a.table_bytes, st, a);
+    hipLaunchKernelGGL(k_rtag_match, dim3(lane_blocks<RT_BLOCK>(a.n)), dim3(RT_BLOCK), a.table_bytes, st, a);
 }
 
 // waves: how many the capture scratch has room for (a multiple of RT_BLOCK / 64)
 void launch_rtag(const RtagArgs &a, bool emit, int waves, hipStream_t st) {
     if (a.n == 0) return;
-    unsigned blocks = rt_blocks(a.n);
+    unsigned blocks = lane_blocks<RT_BLOCK>(a.n);
     const unsigned cap = (unsigned) (waves / (RT_BLOCK / 64));
     if (cap >= 1 && blocks > cap) blocks = cap;
     if (emit) hipLaunchKernelGGL(k_rtag<true>, dim3(blocks), dim3(RT_BLOCK), a.table_bytes, st, a);
@@ -351,5 +337,5 @@ void launch_rtag(const RtagArgs &a, bool emit, int waves, hipStream_t st) {
 
 void launch_rtag_refuse(const RtagArgs &a, const uint32_t *refused, hipStream_t st) {
     if (a.n == 0) return;
-    hipLaunchKernelGGL(k_rtag_refuse, dim3(rt_blocks(a.n)), dim3(RT_BLOCK), 0, st, a, refused);
+    hipLaunchKernelGGL(k_rtag_refuse, dim3(lane_blocks<RT_BLOCK>(a.n)), dim3(RT_BLOCK), 0, st, a, refused);
 }

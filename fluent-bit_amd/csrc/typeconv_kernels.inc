@@ -1,12 +1,11 @@
 // typeconv_kernels.inc -- filter_type_converter (plugins/filter_type_converter/type_converter.c:182-353, src/flb_typecast.c): a lane
 // per record.  ONE function, tc_record, writes a record into whatever sink it is given: the size pass hands it a CountSink, the emit
-// pass a TcSink that never stores outside the row's own [out_off[r], out_off[r + 1]).  Both passes therefore walk the same code; a
+// pass a BoundedSink that never stores outside the row's own [out_off[r], out_off[r + 1]).  Both passes therefore walk the same code; a
 // row whose emitted length is not its sized length (or that ran into the end of its room) is counted, not written past.  The
-// original entries go out as rm_walk / mp_canon re-pack them (runs of already-canonical entries as one span); behind them, for every
+// original entries go out as put_entries re-packs them (runs of already-canonical entries as one span); behind them, for every
 // rule whose key the ORIGINAL body holds, to_key and the converted value -- or the value as it was when the conversion fails.
 // Nested values are never interpreted, only walked; the numbers come from numconv.hpp and write straight into the sink.
-// Included inside namespace flbgpu after kdev.inc, canon_walk.inc (rm_walk, RM_MAP_HDR), ra_lds.inc (the key lookup) and tc_sink.inc
-// (TcSink and the body header's room).
+// Included inside namespace flbgpu after kdev.inc, lane_rows.inc, canon_walk.inc (the sinks' helpers) and ra_lds.inc (the key lookup).
 
 struct TcTable {
     const LDS_AS uint32_t *w;       // the table's words in LDS
@@ -107,53 +106,28 @@ struct TcRow {
     uint64_t len;                       // output bytes (0: nothing emitted)
 };
 
-// the time the encoder writes: flb_log_event_encoder_set_timestamp refuses a time outside the EventTime range, its answer is
-// overwritten (:252-257) and the record goes out with the zero time begin_record left
-DEV void tc_time(const Event &ev, uint32_t &sec, uint32_t &nsec) {
-    const bool ok = ev.sec >= 0 && (uint64_t) ev.sec <= 0xffffffffull && ev.nsec >= 0 && ev.nsec < 1000000000LL;
-    sec = ok ? (uint32_t) ev.sec : 0;
-    nsec = ok ? (uint32_t) ev.nsec : 0;
-}
-
 // one record of the loop (:240-318) into s; false: the row is not one well-formed event
 template <class S> DEV bool tc_record(const TcTable &tb, const Event &ev, const uint8_t *end, S &s, TcRow &w) {
     uint32_t sec, nsec;
-    tc_time(ev, sec, nsec);
-    s.put32(0x00d79292u);
-    s.put32(__builtin_bswap32(sec));
-    s.put32(__builtin_bswap32(nsec));
-    if (ev.meta) mp_canon(ev.meta, ev.meta_end, s); else s.put(0x80);
-    uint8_t *hdr = tc_open_hdr(s);
+    event_time_or_zero(ev, sec, nsec);                                // (its answer is overwritten, :252-257)
+    put_event_head(s, sec, nsec);
+    put_meta(s, ev);
+    uint8_t *hdr = open_map32(s);
     Tok bm = mp_tok(ev.body, end);
-    // the original entries, in order: runs of entries whose encoding is already canonical go out as one span
-    const uint8_t *p = bm.next, *span = nullptr;
-    for (uint32_t i = 0; i < bm.len; i++) {
-        const uint8_t *e0 = p;
-        uint64_t es = 0;
-        bool canon = true;
-        const uint8_t *v = rm_walk(p, end, 2, es, canon);
-        if (!v) return false;
-        p = rm_walk(v, end, 2, es, canon);
-        if (!p) return false;
-        if (canon) { if (!span) span = e0; continue; }
-        if (span) { tc_span(s, span, (uint64_t) (e0 - span)); span = nullptr; }
-        mp_canon(e0, end, s, 2);
-        mp_canon(v, end, s, 2);
-    }
-    if (p != end) return false;                                       // the row is one event and nothing else
-    if (span) tc_span(s, span, (uint64_t) (p - span));
+    // the original entries, in order
+    if (!put_entries(s, bm, end, [](uint32_t, const uint8_t *, const uint8_t *) { return ENTRY_KEEP; })) return false;
     uint64_t found = 0;
     for (int ri = 0; ri < tb.nrules; ri++) {
         const uint8_t *v = tc_lookup(tb, ri, ev.body, end);
         if (!v) continue;
         found++;
         const LDS_AS uint32_t *r = tb.w + TC_RULE_WORDS * (uint32_t) ri;
-        tc_put_lds(s, tb.w + (r[4] >> 2), r[3]);
+        put_lds(s, tb.w + (r[4] >> 2), r[3]);
         bool undef = false;
         if (tc_convert(r[0], v, end, s, undef)) { w.done++; w.undef += undef ? 1u : 0u; }
         else { w.failed++; mp_canon(v, end, s, 2); }
     }
-    tc_close_hdr(s, hdr, (uint64_t) bm.len + found);
+    close_map32(s, hdr, (uint64_t) bm.len + found);
     return true;
 }
 
@@ -179,34 +153,22 @@ DEV bool tc_emit(const TypeconvArgs &a, const TcTable &tb, uint64_t r) {
     Event ev = decode_event(rec, end, true);
     if (ev.flags & RF_BAD) return false;
     uint8_t *o0 = a.out + a.out_off[r], *o1 = a.out + a.out_off[r + 1];
-    TcSink bs(o0, o1);
+    BoundedSink bs(o0, o1);
     TcRow w;
     w.bad = false; w.decoded = false; w.done = 0; w.failed = 0; w.undef = 0; w.len = 0;
     const bool ok = tc_record(tb, ev, end, bs, w);
     return ok && !bs.over && bs.p == o1;
 }
 
-DEV unsigned long long tc_wave_sum(unsigned long long v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 template <bool EMIT>
 __global__ void __launch_bounds__(TC_BLOCK) k_typeconv(TypeconvArgs a) {
-    LDS_AS uint32_t *lds = (LDS_AS uint32_t *) g_lds;
-    for (uint32_t i = threadIdx.x; i < a.table_bytes / 4; i += TC_BLOCK) lds[i] = a.table[i];
+    TcTable tb{lane_stage_table<TC_BLOCK>(a.table, a.table_bytes), a.nrules};
     __syncthreads();
-    TcTable tb{lds, a.nrules};
-    const uint64_t gsz = (uint64_t) gridDim.x * TC_BLOCK;
-    const uint32_t lane = threadIdx.x & 63u;
     unsigned long long n_dec = 0, n_out = 0, n_done = 0, n_failed = 0, n_undef = 0, n_big = 0, n_mis = 0;
-    // every wave walks in step (the trip count is the wave's, not the lane's): the ballots below see whole waves
-    for (uint64_t r0 = (uint64_t) blockIdx.x * TC_BLOCK + (threadIdx.x & ~63u); r0 < a.n; r0 += gsz) {
-        const uint64_t r = r0 + lane;
-        const bool live = r < a.n;
+    lane_wave_rows<TC_BLOCK>(a.n, [&](uint64_t r, bool live) {
         if (EMIT) {
             if (live && a.len[r] && !tc_emit(a, tb, r)) n_mis++;
-            continue;
+            return;
         }
         TcRow w;
         w.bad = false; w.decoded = false; w.done = 0; w.failed = 0; w.undef = 0; w.len = 0;
@@ -218,30 +180,19 @@ __global__ void __launch_bounds__(TC_BLOCK) k_typeconv(TypeconvArgs a) {
             n_done += w.done; n_failed += w.failed; n_undef += w.undef;
             if (w.bad) atomicMin(a.first_bad, (unsigned long long) r);
         }
-        // the call-level facts of a wave's 64 records: counted by one lane from the ballots
-        const unsigned long long b_dec = __ballot(w.decoded), b_out = __ballot(w.len != 0);
-        if (lane == 0) { n_dec += __popcll(b_dec); n_out += __popcll(b_out); }
-    }
-    if (EMIT) {
-        if (n_mis) atomicAdd(&a.counts[6], n_mis);
-        return;
-    }
+        lane_count(n_dec, w.decoded); lane_count(n_out, w.len != 0);
+    });
+    if (EMIT) { lane_flush(&a.counts[6], n_mis); return; }
     // one atomic per wave and counter that is not zero (every lane of the wave is here: the loop's trip count is the wave's)
-    n_done = tc_wave_sum(n_done); n_failed = tc_wave_sum(n_failed); n_undef = tc_wave_sum(n_undef);
-    if (lane == 0) {
-        if (n_dec) atomicAdd(&a.counts[0], n_dec);
-        if (n_out) atomicAdd(&a.counts[1], n_out);
-        if (n_done) atomicAdd(&a.counts[2], n_done);
-        if (n_failed) atomicAdd(&a.counts[3], n_failed);
-        if (n_undef) atomicAdd(&a.counts[4], n_undef);
-    }
-    if (n_big) atomicAdd(&a.counts[5], n_big);
+    n_done = lane_wave_sum(n_done); n_failed = lane_wave_sum(n_failed); n_undef = lane_wave_sum(n_undef);
+    lane_flush(&a.counts[0], n_dec); lane_flush(&a.counts[1], n_out);                                         // (lane 0's)
+    if ((threadIdx.x & 63u) == 0) { lane_flush(&a.counts[2], n_done); lane_flush(&a.counts[3], n_failed); lane_flush(&a.counts[4], n_undef); }
+    lane_flush(&a.counts[5], n_big);
 }
 
 void launch_typeconv(const TypeconvArgs &a, bool emit, hipStream_t st) {
     if (a.n == 0) return;
-    uint64_t blocks = (a.n + TC_BLOCK - 1) / TC_BLOCK;
-    if (blocks > 65536) blocks = 65536;
-    if (emit) hipLaunchKernelGGL(k_typeconv<true>, dim3((unsigned) blocks), dim3(TC_BLOCK), a.table_bytes, st, a);
-    else hipLaunchKernelGGL(k_typeconv<false>, dim3((unsigned) blocks), dim3(TC_BLOCK), a.table_bytes, st, a);
+    const dim3 g(lane_blocks<TC_BLOCK>(a.n)), b(TC_BLOCK);
+    if (emit) hipLaunchKernelGGL(k_typeconv<true>, g, b, a.table_bytes, st, a);
+    else hipLaunchKernelGGL(k_typeconv<false>, g, b, a.table_bytes, st, a);
 }

@@ -628,6 +628,9 @@ int flbgpu_filter_host_rules(flbgpu_filter *f, uint64_t *out4);
  * run accumulates the duration of each kernel; names[] is a NUL-separated list. */
 void flbgpu_filter_profile(flbgpu_filter *f, int enable);
 int flbgpu_filter_profile_read(flbgpu_filter *f, int max, const char **names, double *ms, uint64_t *launches);
+/* host only, no device: the most blocks a launch of the lane-per-record filters gets -- 65536, or what the test switch
+ * FLBGPU_LANE_MAX_BLOCKS=<1 ... 65536> (read once per process) names. */
+unsigned flbgpu_lane_max_blocks(void);
 
 /* ---- msgpack -> JSON: replaces flb_pack_msgpack_to_json_format ------------------------------------
  * src/flb_pack.c:1320-1600 (what out_stdout / out_http / out_kafka / out_file ... call on every flushed chunk) with

@@ -64,6 +64,23 @@ def test_fixture_cases(g, case):
     assert got == (case["ret"], base64.b64decode(case["out"]) if case["out"] is not None else None)
 
 
+def mixed_records(n):
+    """every third record holds `agent` and loses it, the others go through the walk and keep all they have"""
+    return b"".join(synth.mp([[synth.ext_ts(1700000000 + i, i), {}],
+                              synth.KV([(b"host", b"h%d" % (i % 9))] + ([(b"agent", b"a" * (i % 23))] if i % 3 == 0 else []) + [(b"size", 1000 + i)])])
+                    for i in range(n))
+
+
+@pytest.mark.parametrize("n", [1, 63, 64, 65, 255, 256, 257, 1025])
+def test_wave_and_block_edges(g, n):
+    data = mixed_records(n)
+    assert data.count(b"\xa5agent") == (n + 2) // 3
+    for props in (R1, [("Remove_key", "agent")]):
+        ret, out = same_props(g, props, data)
+        assert ret == g.MODIFIED and len(synth.unpack_all(out)) == n
+        assert out.count(b"\xa5agent") == 0 and out.count(b"\xa8hostname") == (n if props is R1 else 0)
+
+
 KEYS = [b"a", b"A", b"ab", b"AB", b"aB", b"abc", b"ABCD", b"abcde", b"host", b"Host", b"HOSTNAME", b"k", b"k1", b"K2", b"log", b"",
         b"x" * 9, b"X" * 9, b"x" * 40, "é".encode(), "É".encode(), b"a\0b", b"ab\0"]
 TABLE = ["a", "A", "ab", "Ab*", "abc", "abcd*", "host", "HOST*", "k*", "K1", "log", "*", "x" * 9, "X" * 8 + "*", "x" * 40, "é", "É*",
