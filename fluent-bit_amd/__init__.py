@@ -150,6 +150,8 @@ def lib():
     L.flbgpu_l2m_seq_sums.restype = c_int64
     L.flbgpu_l2m_seq_sums.argtypes = [c_void_p, c_uint64, POINTER(c_double)]
     L.flbgpu_seqsum_dev.argtypes = [c_void_p, c_void_p, c_uint64, ctypes.c_uint32, c_void_p]
+    L.flbgpu_l2m_stale_dev.argtypes = [c_void_p, c_void_p, c_uint64, c_uint64]
+    L.flbgpu_l2m_aggregate_dev.argtypes = [c_int, c_void_p, c_void_p, c_uint64, c_uint64, c_uint64, ctypes.c_uint32, c_int, c_void_p, c_void_p]
     L.flbgpu_host_phases.restype = ctypes.c_int
     L.flbgpu_host_phases.argtypes = [ctypes.POINTER(ctypes.c_double), ctypes.c_int]
     L.flbgpu_filter_host_rules.restype = ctypes.c_int
@@ -1246,6 +1248,37 @@ def finalize_row(mode, nbuckets, row):
     bk = np.zeros(nbuckets + 1, dtype=np.uint64)
     lib().flbgpu_l2m_finalize_row(mode, nbuckets, row.ctypes.data, byref(v), bk.ctypes.data, byref(cnt), byref(sm))
     return dict(value=v.value, buckets=[int(x) for x in bk], count=cnt.value, sum=sm.value)
+
+
+def l2m_row_words(mode, nbuckets=0):
+    """words of a series row (csrc/dev.hpp l2m_row_words)"""
+    return 76 + nbuckets if mode == HISTOGRAM else 4
+
+
+def l2m_stale_dev(sid, val_bits, first_bad=2 ** 64 - 1):
+    """flbgpu_l2m_stale_dev (a test aid): the stale scan's kernels on copies of the columns -> (sid, val_bits) as they leave it"""
+    import numpy as np
+    sid = np.array(sid, dtype=np.uint32)
+    vb = np.array(val_bits, dtype=np.uint64)
+    assert sid.shape == vb.shape and sid.ndim == 1
+    if lib().flbgpu_l2m_stale_dev(sid.ctypes.data, vb.ctypes.data, len(sid), first_bad) != 0:
+        raise RuntimeError("flbgpu_l2m_stale_dev: " + last_error())
+    return sid, vb
+
+
+def l2m_aggregate_dev(mode, sid, val_bits, rows, first_bad=2 ** 64 - 1, idx_base=0, bounds=()):
+    """flbgpu_l2m_aggregate_dev (a test aid): one call's columns aggregated into a copy of rows[nseries][l2m_row_words] -> that copy"""
+    import numpy as np
+    sid = np.ascontiguousarray(sid, dtype=np.uint32)
+    vb = None if val_bits is None else np.ascontiguousarray(val_bits, dtype=np.uint64)
+    bd = np.ascontiguousarray(bounds, dtype=np.float64)
+    rows = np.array(rows, dtype=np.uint64)
+    nb = len(bd) if mode == HISTOGRAM else 0
+    assert rows.ndim == 2 and rows.shape[1] == l2m_row_words(mode, nb) and (vb is None or vb.shape == sid.shape)
+    if lib().flbgpu_l2m_aggregate_dev(mode, sid.ctypes.data, None if vb is None else vb.ctypes.data, len(sid), first_bad, idx_base,
+                                      rows.shape[0], nb, bd.ctypes.data if nb else None, rows.ctypes.data) != 0:
+        raise RuntimeError("flbgpu_l2m_aggregate_dev: " + last_error())
+    return rows
 
 
 class FilterLogToMetrics(_Filter):

@@ -532,10 +532,21 @@ int flbgpu_l2m_finalize_row(int mode, int nbuckets, const uint64_t *row, double 
  * flbgpu_seqsum_dev (a test aid, no filter behind it): the kernels of that sum on host columns the caller supplies -- observation i
  * belongs to series sid[i] (an id >= nseries is no observation) and has the binary64 bits val_bits[i]; seq_inout[nseries] holds the
  * start sums and gets the results.  The columns are copied to the device, the kernels run, the sums are copied back; 0, or -1 with
- * flbgpu_last_error (there is no host path behind it).  n == 0 or nseries == 0 leaves seq_inout alone and returns 0. */
+ * flbgpu_last_error (there is no host path behind it).  n == 0 or nseries == 0 leaves seq_inout alone and returns 0.
+ * flbgpu_l2m_stale_dev / flbgpu_l2m_aggregate_dev (test aids, no filter behind them): the stale scan and the aggregation kernels on host
+ * columns the caller supplies, as the extraction would have written them -- sid[i] is a series id, 0xFFFFFFFF (no observation),
+ * 0xFFFFFFFE (deferred) or an id with bit 31 set (stale: takes the value of the closest earlier row that assigned one), val_bits[i]
+ * the binary64 bits; rows at or behind first_bad never ran (UINT64_MAX: none).  stale_dev rewrites both columns in place.
+ * aggregate_dev (mode 0 counter, 1 gauge, 2 histogram; val_bits may be NULL for a counter) adds the call to rows_inout[nseries][W],
+ * W the row_words flbgpu_l2m_info reports for that mode and nbuckets (4, or 76 + nbuckets for a histogram), with the gauge / carry
+ * epilogue of the filter; idx_base is the global index of row 0, so calls chain through rows_inout.  An id >= nseries in front of
+ * first_bad is refused.  0, or -1 with flbgpu_last_error; n == 0 or nseries == 0 changes nothing and returns 0. */
 int flbgpu_l2m_set_sum_order(flbgpu_filter *f, int reference);
 int64_t flbgpu_l2m_seq_sums(flbgpu_filter *f, uint64_t max_series, double *sums);
 int flbgpu_seqsum_dev(const uint32_t *sid, const uint64_t *val_bits, uint64_t n, uint32_t nseries, double *seq_inout);
+int flbgpu_l2m_stale_dev(uint32_t *sid, uint64_t *val_bits, uint64_t n, uint64_t first_bad);
+int flbgpu_l2m_aggregate_dev(int mode, const uint32_t *sid, const uint64_t *val_bits, uint64_t n, uint64_t first_bad, uint64_t idx_base,
+                             uint32_t nseries, int nbuckets, const double *bounds, uint64_t *rows_inout);
 int flbgpu_l2m_chain_begin(flbgpu_filter *f, uint64_t n_keys, const uint64_t *key_off, const char *keys, double *sums);
 int flbgpu_l2m_seq_replay(flbgpu_filter *f, uint64_t n_keys, const uint64_t *key_off, const char *keys, double *sums);
 int flbgpu_l2m_chain_end(flbgpu_filter *f, uint64_t n_keys, const uint64_t *key_off, const char *keys, const double *sums);
