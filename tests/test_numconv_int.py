@@ -7,6 +7,7 @@ import random
 import struct
 
 import flbamd_loader
+from numconv_cases import (CAST_D2U_IN_RANGE, CAST_I64, CAST_U64, CAST_X86_I64, CAST_X86_U64, EDGES, NANS, gen_int_strings)
 
 g = flbamd_loader.load()
 L = g.lib()
@@ -46,17 +47,6 @@ def check(s):
             assert ours(s, base, signed) == libc(s, base, signed), (s, base, signed)
 
 
-EDGES = [b"", b" ", b"0", b"-0", b"+0", b"  -0", b"7", b" 7", b"\t7", b"\n7", b"\v7", b"\f7", b"\r7", b"\x0b\x0c \t\r\n-7", b"\x1c7", b"\xa07",
-         b"-", b"+", b"-+1", b"+-1", b"--1", b"- 1", b"1 2", b"12abc", b"abc", b"1.5", b"1e3", b"0x", b"0X", b"0xg", b"0x g", b"0x1f", b"0X1F", b"-0x1f",
-         b"+0x", b"0x-1", b"x1f", b"00x1f", b"0b1", b"1f", b"ff", b"g", b"9223372036854775806", b"9223372036854775807",
-         b"9223372036854775808", b"-9223372036854775807", b"-9223372036854775808", b"-9223372036854775809", b"18446744073709551614",
-         b"18446744073709551615", b"18446744073709551616", b"18446744073709551617", b"-18446744073709551615", b"-18446744073709551616",
-         b"-1", b"7fffffffffffffff", b"8000000000000000", b"-8000000000000000", b"-8000000000000001", b"ffffffffffffffff",
-         b"0xffffffffffffffff", b"10000000000000000", b"0x10000000000000001", b"123456789012345678901234567890",
-         b"-123456789012345678901234567890", b"abcdefabcdefabcdefabcdefabcdef", b"1\x002", b"\x001", b" \x00 1", b"0x\x001", b"12\x00",
-         b"0" * 40 + b"5", b"-" + b"0" * 40 + b"5", b"0x" + b"0" * 40 + b"f"]
-
-
 def test_hand_picked_edges():
     for s in EDGES:
         check(s)
@@ -72,12 +62,7 @@ def test_hand_picked_edges():
 
 def test_200000_random_strings():
     r = random.Random(20261018)
-    alphabet = b"0123456789" * 3 + b"abcdefABCDEFxX" + b"+- \t\n\v\f\r" + b"gz.\x00\xff"
-    heads = [b"", b"", b"", b" ", b"-", b"+", b"0x", b"-0x", b" 0X", b"\t-", b"1844674407370955161", b"922337203685477580", b"-922337203685477580",
-             b"ffffffffffffffff", b"7fffffffffffffff"]
-    for _ in range(200000):
-        n = r.choice((0, 1, 2, 3, 5, 8, 17, 19, 20, 21, 33))
-        s = r.choice(heads) + bytes(r.choice(alphabet) for _ in range(n))
+    for s in gen_int_strings(r, 200000):
         check(s)
 
 
@@ -121,12 +106,6 @@ def scan(s, mode):
     return st, struct.pack("<d", d.value), used.value
 
 
-NANS = [b"nan", b"-nan", b"nan()", b"nan(0)", b"nan(1)", b"-nan(1)", b"nan(0x12)", b"NAN(0X7ffffffffffff)", b"nan(0xfffffffffffff)", b"nan(0x8000000000000)",
-        b"nan(0xffffffffffffffff)", b"nan(0x1ffffffffffffffff)", b"nan(123)", b"nan(0123)", b"nan(08)", b"nan(abc)", b"nan(12ab)", b"nan(0x)", b"nan(0xg)",
-        b"nan(_)", b"nan(1_)", b"nan(0b1)", b"nan(18446744073709551615)", b"nan(99999999999999999999)", b"nan(2251799813685248)", b"nan(2251799813685247)",
-        b"nan(12", b"nan(1 )", b"nan(-1)", b"nan(+1)", b"nan( 1)", b"nan(1)x", b"  +nan(7)rest", b"nan(0x12", b"nan(\x00)"]
-
-
 def test_nan_payload_mode_against_strtod():
     end = ctypes.c_char_p()
     for s in NANS:
@@ -148,10 +127,10 @@ def test_nan_payload_mode_against_strtod():
 
 def test_casts():
     r = random.Random(11)
-    ints = [0, 1, -1, 2 ** 53, 2 ** 53 + 1, 2 ** 53 + 3, 2 ** 63 - 1, -2 ** 63, 2 ** 63 - 513, 2 ** 63 - 512, 9007199254740993] + [r.randrange(-2 ** 63, 2 ** 63) for _ in range(20000)]
+    ints = CAST_I64 + [r.randrange(-2 ** 63, 2 ** 63) for _ in range(20000)]
     for v in ints:
         assert L.flbgpu_nc_int_to_double(v & M64, 1) == float(v)
-    for v in [0, 1, 2 ** 63, 2 ** 64 - 1, 2 ** 64 - 1024, 2 ** 64 - 1025, 2 ** 63 + 1025] + [r.getrandbits(64) for _ in range(20000)]:
+    for v in CAST_U64 + [r.getrandbits(64) for _ in range(20000)]:
         assert L.flbgpu_nc_int_to_double(v, 0) == float(v)
     u = ctypes.c_int()
     # inside the targets' ranges: the C cast
@@ -163,12 +142,10 @@ def test_casts():
             assert L.flbgpu_nc_double_to_int(v, 1, ctypes.byref(u)) == int(v) & M64 and u.value == 0
         if -1.0 < v < 2.0 ** 64:
             assert L.flbgpu_nc_double_to_int(v, 0, ctypes.byref(u)) == int(v) and u.value == 0
-    for v in (0.9, -0.9, 1.5, 2.0 ** 63 - 1024, 2.0 ** 63, 2.0 ** 64 - 2048, 123.456):
+    for v in CAST_D2U_IN_RANGE:
         assert L.flbgpu_nc_double_to_int(v, 0, ctypes.byref(u)) == int(v) and u.value == 0
     # outside: x86-64's answers, counted
-    MIN = 1 << 63
-    for v, want in ((float("nan"), MIN), (float("inf"), MIN), (float("-inf"), MIN), (2.0 ** 63, MIN), (-(2.0 ** 63), MIN), (1e300, MIN), (-1e300, MIN)):
+    for v, want in CAST_X86_I64:
         assert L.flbgpu_nc_double_to_int(v, 1, ctypes.byref(u)) == want and u.value == 1, v
-    for v, want in ((float("nan"), MIN), (float("inf"), 0), (float("-inf"), MIN), (2.0 ** 64, 0), (1e300, 0), (-1.0, M64), (-1.5, M64), (-5.0, M64 - 4),
-                    (-(2.0 ** 63), MIN), (-1e300, MIN)):
+    for v, want in CAST_X86_U64:
         assert L.flbgpu_nc_double_to_int(v, 0, ctypes.byref(u)) == want and u.value == 1, v
