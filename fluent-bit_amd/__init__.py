@@ -96,6 +96,20 @@ def lib():
     L.flbgpu_expect_failure_text.argtypes = [c_void_p, c_uint64, c_char_p, c_size_t]
     L.flbgpu_expect_text_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_uint64, ctypes.c_uint32, ctypes.c_uint32, c_char_p, c_size_t,
                                            c_char_p, c_size_t]
+    L.flbgpu_filter_throttle_size_create.restype = c_void_p
+    L.flbgpu_filter_throttle_size_create.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p)]
+    L.flbgpu_throttle_size_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
+    L.flbgpu_throttle_size_tick.argtypes = [c_void_p, ctypes.c_int64]
+    L.flbgpu_throttle_size_set_now.argtypes = [c_void_p, ctypes.c_int64]
+    L.flbgpu_throttle_size_counters.restype = None
+    L.flbgpu_throttle_size_counters.argtypes = [c_void_p, POINTER(c_uint64)]
+    L.flbgpu_throttle_size_windows.argtypes = [c_void_p, c_void_p]
+    L.flbgpu_filter_throttle_create.restype = c_void_p
+    L.flbgpu_filter_throttle_create.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p)]
+    L.flbgpu_throttle_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
+    L.flbgpu_throttle_tick.argtypes = [c_void_p, ctypes.c_int64]
+    L.flbgpu_throttle_counters.restype = None
+    L.flbgpu_throttle_counters.argtypes = [c_void_p, POINTER(c_uint64)]
     L.flbgpu_filter_kubernetes_create.restype = c_void_p
     L.flbgpu_filter_kubernetes_create.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p)]
     L.flbgpu_kubernetes_parse_check.argtypes = [c_int, POINTER(c_char_p), POINTER(c_char_p), c_char_p, c_size_t]
@@ -540,6 +554,73 @@ def expect_text_check(props, rule, kind, vtype, value=b""):
     if lib().flbgpu_expect_text_check(*_props(props), rule, kind, vtype, value, len(value), buf, len(buf)) < 0:
         raise ValueError(last_error())
     return buf.value
+
+
+class TszWindows(ctypes.Structure):
+    _fields_ = [("count", c_uint64), ("window", ctypes.c_uint32), ("names", c_void_p), ("name_off", POINTER(c_uint64)), ("total", POINTER(c_uint64)),
+                ("timestamp", POINTER(ctypes.c_int64)), ("head", POINTER(ctypes.c_int32)), ("pane_size", POINTER(c_uint64)),
+                ("pane_ts", POINTER(ctypes.c_int64))]
+
+
+class FilterThrottleSize(_PropsFilter):
+    """filter_throttle_size: props = [(name, value), ...], e.g. [("rate", "1k"), ("window", "5"), ("name_field", "kubernetes|pod"),
+    ("log_field", "log")] (plugins/filter_throttle_size/throttle_size.c).  The windows live on the device from call to call; the
+    ticker thread is the caller's: tick() is one trip of it"""
+    _CREATE = "flbgpu_filter_throttle_size_create"
+
+    def tick(self, seconds=0):
+        """one trip of the ticker at `seconds` (0: the host clock)"""
+        if lib().flbgpu_throttle_size_tick(self.h, int(seconds)) != 0:
+            raise RuntimeError(last_error())
+
+    def set_now(self, seconds):
+        """the time a window created by the next calls gets (0: the host clock again)"""
+        if lib().flbgpu_throttle_size_set_now(self.h, int(seconds)) != 0:
+            raise RuntimeError(last_error())
+
+    def counters(self):
+        """since create: dict(records, kept, dropped, exempt, live, created, deleted, grows, names) (flb_gpu.h flbgpu_throttle_size_counters)"""
+        o = (c_uint64 * 9)()
+        lib().flbgpu_throttle_size_counters(self.h, o)
+        return dict(zip(("records", "kept", "dropped", "exempt", "live", "created", "deleted", "grows", "names"), (int(x) for x in o)))
+
+    def windows(self):
+        """the live windows: {name bytes: dict(total, timestamp, head, panes=[(timestamp, size), ...])} (downloaded on request)"""
+        w = TszWindows()
+        if lib().flbgpu_throttle_size_windows(self.h, byref(w)) != 0:
+            raise RuntimeError(last_error())
+        names = ctypes.string_at(w.names, w.name_off[w.count]) if w.count else b""
+        out = {}
+        for i in range(w.count):
+            panes = [(int(w.pane_ts[i * w.window + p]), int(w.pane_size[i * w.window + p])) for p in range(w.window)]
+            out[names[w.name_off[i]:w.name_off[i + 1]]] = dict(total=int(w.total[i]), timestamp=int(w.timestamp[i]), head=int(w.head[i]), panes=panes)
+        return out
+
+
+def throttle_size_parse_check(props):
+    """the resolved configuration as one line of text (host only); raises ValueError where create refuses"""
+    return _parse_check("flbgpu_throttle_size_parse_check", props, 1 << 17)
+
+
+class FilterThrottle(_PropsFilter):
+    """filter_throttle: props of rate, window, interval, print_status (plugins/filter_throttle/throttle.c).  A call keeps its first
+    K records; tick() is one trip of the ticker, which stays with the caller"""
+    _CREATE = "flbgpu_filter_throttle_create"
+
+    def tick(self, seconds=0):
+        if lib().flbgpu_throttle_tick(self.h, int(seconds)) != 0:
+            raise RuntimeError(last_error())
+
+    def counters(self):
+        """since create: (records in, kept, dropped)"""
+        o = (c_uint64 * 3)()
+        lib().flbgpu_throttle_counters(self.h, o)
+        return tuple(int(x) for x in o)
+
+
+def throttle_parse_check(props):
+    """the resolved configuration as one line of text (host only); raises ValueError where create refuses"""
+    return _parse_check("flbgpu_throttle_parse_check", props, 1 << 12)
 
 
 class RtagEmittedRec(ctypes.Structure):

@@ -2411,7 +2411,7 @@ static int run_any_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_
         ok = run_l2m_dev(f, in, st, &ret);
         if (ok && ret == FLBGPU_FILTER_MODIFIED && out) memset(out, 0, sizeof(*out));   // discard_logs: every record dropped
     }
-    else if (f->kind >= F_MODIFY && f->kind <= F_KUBE) ok = f->state->run(f, in, out, st, &ret, garbage);
+    else if (f->kind >= F_MODIFY && f->kind <= F_THROTTLE) ok = f->state->run(f, in, out, st, &ret, garbage);
     else ok = f->kind == F_PARSER ? run_parser_dev(f, in, out, st, &ret) : run_grep_dev(f, in, out, st, &ret, garbage);
     if (!ok) return FLBGPU_FILTER_NOTOUCH;      // errors degrade to NOTOUCH (SURVEY 8b "Errors")
     return ret;

@@ -160,9 +160,10 @@ uint64_t l2m_limbs_bits(const uint64_t *limbs, uint64_t n_nan, uint64_t n_pinf, 
 struct KernelProf { const char *name; double ms = 0; uint64_t launches = 0; };
 struct ProfPending { const char *name; hipEvent_t e0, e1; };
 
-enum { F_PARSER = 1, F_GREP = 2, F_L2M = 3, F_JSONFMT = 4, F_MODIFY = 5, F_RECMOD = 6, F_NEST = 7, F_TYPECONV = 8, F_RTAG = 9, F_MLFILTER = 10, F_CHECKLIST = 11, F_EXPECT = 12, F_KUBE = 13 };
+enum { F_PARSER = 1, F_GREP = 2, F_L2M = 3, F_JSONFMT = 4, F_MODIFY = 5, F_RECMOD = 6, F_NEST = 7, F_TYPECONV = 8, F_RTAG = 9, F_MLFILTER = 10, F_CHECKLIST = 11, F_EXPECT = 12, F_KUBE = 13,
+       F_THROTTLE_SIZE = 14, F_THROTTLE = 15 };
 
-// What a lane-per-record filter (kinds F_MODIFY .. F_KUBE) keeps behind its flbgpu_filter: its program and its buffers, which
+// What a lane-per-record filter (kinds F_MODIFY .. F_THROTTLE) keeps behind its flbgpu_filter: its program and its buffers, which
 // release themselves (ScopedDevBuf, ScopedPinnedBuf), and one cb_filter call on a device chunk.  garbage: undecodable bytes follow the
 // rows.  false: failure (flbgpu_last_error says which); *ret may be -1 where the filter hands a call back.
 struct FilterState {
@@ -235,7 +236,7 @@ struct flbgpu_filter {
     // filter_log_to_metrics whose regex / exclude rules hold a pattern that is not a regular expression: the rules live in this hidden
     // filter_grep (host rules, flbgpu.cpp) and run in FRONT of the metric kernels, which then see the kept records and no rules
     flbgpu_filter *l2m_gate = nullptr;
-    // filter_modify, record_modifier, nest, type_converter, rewrite_tag, multiline, checklist, expect, kubernetes: the one that `kind` names (filter_host.hpp)
+    // filter_modify, record_modifier, nest, type_converter, rewrite_tag, multiline, checklist, expect, kubernetes, throttle_size, throttle: the one that `kind` names (filter_host.hpp)
     FilterState *state = nullptr;
     // filter_rewrite_tag during a host-level call (flbgpu_filter_chain_run): the emitter's callback is asked, and the chunk at
     // rtag_dev_base is the caller's buffer at rtag_host_base (filter_expect: its failure table's offsets index that buffer)

@@ -409,6 +409,75 @@ void flbgpu_kubernetes_counters(flbgpu_filter *f, uint64_t out[4]);
  * bytes a workgroup of the emit pass takes */
 void flbgpu_kubernetes_layout(flbgpu_filter *f, uint64_t out[3]);
 
+/* ---- filter_throttle_size: replaces cb_throttle_size_init / cb_throttle_size_filter and one trip of size_time_ticker ----
+ * plugins/filter_throttle_size/throttle_size.c:308-433 (throttle_data_by_size), 169-192 (the ticker), 478-657 (configure, init),
+ * 659-736 (one call); size_window.h:59-91, size_window.c:42-91.  (names[i], values[i]) are the instance's properties, names without
+ * case; the plugin has no config map, so any other name is accepted and not looked at:
+ *   rate (flb_utils_size_to_bytes; <= 0 or unparsable: 1048576), window (strtoul; must be > 1, else 5), interval and
+ *   window_time_duration (parse_duration: a truncating int with an s/m/h/d suffix; 1 and 60; the duration is raised to
+ *   interval * window), name_field and log_field (`|`-separated paths, flb_utils_split(.., 20)), print_status and hash_table_size
+ *   (no effect on the records).
+ * A record whose name field is missing or neither STR nor BIN, or whose log field is missing, is kept and touches no window
+ * ("exempt").  Every other record's load -- the payload bytes of every STR and BIN inside the log field, or inside the whole body --
+ * goes through the greedy admission of its name's window, in record order per name.  The windows live in HBM from call to call.
+ * The call answers NOTOUCH when every record was kept, else MODIFIED with the kept records' own bytes (an empty buffer when none
+ * was).  The ticker thread stays with the caller: flbgpu_throttle_size_tick is one trip of it.  Tick, set_now, the views and a run
+ * on one filter are serialised by the filter, and each selects the device the filter was created on (HIP's current device is per
+ * thread), so a timer thread may call tick.
+ * The panes take 16 bytes a pane and name: a filter starts with room for fewer names the larger its window is (256 MiB of panes at
+ * most) and grows on demand; a call that would take the panes past 16 GiB fails (NOTOUCH + last_error naming names and window).
+ * create answers NULL + last_error for a window over 65536 panes, a duration parse_duration cannot hold in an int, a path table
+ * over 32768 bytes.  Test switches read at create: FLBGPU_TSZ_DICT_SLOTS=<n> (initial dictionary capacity), FLBGPU_TSZ_HASH_BITS=<n>
+ * (only the low n bits of a name's hash are kept), FLBGPU_TSZ_WAVE_MIN=<rows> (segment length from which a wave admits; 64).
+ * Runs through flbgpu_filter_run[_dev], flbgpu_filter_chain_run[_dev], flbgpu_filter_last_counts (records in / records kept) and
+ * flbgpu_filter_destroy. */
+flbgpu_filter *flbgpu_filter_throttle_size_create(int nprops, const char *const *names, const char *const *values);
+/* host only, no device: the resolved configuration as one line of text --
+ * "rate=<%.17g>;window=<n>;interval=<n>;duration=<n, after the raise>;name=<hex>|<hex>...|-;log=<hex>|...|-" -- 0, or -1 +
+ * last_error where create refuses */
+int flbgpu_throttle_size_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap);
+/* one trip of the ticker at time `seconds` (0: the host clock, as the reference treats a zero timestamp): add_new_pane for every
+ * window, then every window with (long) (seconds - window_time_duration) > window.timestamp goes.  0, or -1 + last_error */
+int flbgpu_throttle_size_tick(flbgpu_filter *f, int64_t seconds);
+/* the time a window created by the next calls gets (0: the host clock again).  Before the filter's first run or tick it also dates
+ * the `*` window create made (name_field unset), as if the filter had been created then */
+int flbgpu_throttle_size_set_now(flbgpu_filter *f, int64_t seconds);
+/* since create: out[0] records in, out[1] kept, out[2] dropped, out[3] exempt, out[4] windows live, out[5] windows created,
+ * out[6] windows deleted, out[7] times the dictionary grew; out[8] the names the dictionary holds right now, dead ones included (a
+ * growth drops the dead ones).  A name is entered when its record is read, before any verdict: out[8] also counts names whose
+ * records were all dropped, and names of rows behind a record the decoder refused, which the call itself never judges */
+void flbgpu_throttle_size_counters(flbgpu_filter *f, uint64_t out[9]);
+/* a read-only view of the live windows for tests, downloaded on request only; in window id order.  Window i: its name at
+ * names[name_off[i] .. name_off[i + 1]), total[i], timestamp[i], head[i], and its panes at pane_size / pane_ts[i * window ..].
+ * The pointers are the filter's and hold until its next call. */
+typedef struct flbgpu_tsz_windows {
+    uint64_t count;
+    uint32_t window;
+    const char *names;
+    const uint64_t *name_off;
+    const uint64_t *total;
+    const int64_t *timestamp;
+    const int32_t *head;
+    const uint64_t *pane_size;
+    const int64_t *pane_ts;
+} flbgpu_tsz_windows;
+int flbgpu_throttle_size_windows(flbgpu_filter *f, flbgpu_tsz_windows *out);
+
+/* ---- filter_throttle: replaces cb_throttle_init / cb_throttle_filter and one trip of time_ticker ----
+ * plugins/filter_throttle/throttle.c:101-111 (throttle_data), 72-99 (the ticker), 113-188 (configure, init), 190-272 (one call);
+ * window.c:30-97.  Properties, names without case, of the plugin's config map (:301-328): rate (double; <= 1.0 gives 1), window
+ * (int; <= 1 gives 5), interval (parse_duration: warns on a bad one and takes what strtod read), print_status (a bool; no effect).
+ * The decision does not depend on a record's content: a call keeps its first K records, K from the reference's own comparison
+ * evaluated on the host against the window it keeps there; the device finds the records and copies the first K.  NOTOUCH when all
+ * were kept.  create answers NULL + last_error for an unknown property, a property set twice, a bool that is none, `${` in a value. */
+flbgpu_filter *flbgpu_filter_throttle_create(int nprops, const char *const *names, const char *const *values);
+/* host only: "rate=<%.17g>;window=<n>;interval=<n>" -- 0, or -1 + last_error where create refuses */
+int flbgpu_throttle_parse_check(int nprops, const char *const *names, const char *const *values, char *desc, size_t cap);
+/* one trip of the ticker: window_add(seconds, 0), current_timestamp = seconds (0: the host clock) */
+int flbgpu_throttle_tick(flbgpu_filter *f, int64_t seconds);
+/* since create: out[0] records in, out[1] kept, out[2] dropped */
+void flbgpu_throttle_counters(flbgpu_filter *f, uint64_t out[3]);
+
 /* ---- filter_rewrite_tag: replaces cb_rewrite_tag_init / cb_rewrite_tag_filter / cb_rewrite_tag_exit ----
  * plugins/filter_rewrite_tag/rewrite_tag.c:112-190 (process_config, behind the config map of :590-613), 356-423 (process_record),
  * 425-557 (one call); src/flb_record_accessor.c:74-230 (the parts of an accessor), 456-619 (ra_translate_*), 644-699
