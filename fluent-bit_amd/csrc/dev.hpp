@@ -3,6 +3,7 @@
 #include <cstdint>
 #include <atomic>
 #include "tzif.hpp"
+#include "parser_words.hpp"
 
 namespace flbgpu {
 

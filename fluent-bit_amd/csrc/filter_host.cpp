@@ -40,9 +40,10 @@ bool scan_lengths_wait(flbgpu_filter *f, hipStream_t st, const uint64_t *total) 
     return f->d_out.ensure(*total + 16);
 }
 
-void set_out(flbgpu_filter *f, flbgpu_dev_chunk *out, uint64_t n, uint64_t total) {
-    out->data = f->d_out.p; out->row_off = f->d_off.as<uint64_t>(); out->n = n; out->bytes = total;
+void set_out(const flbgpu_filter *bytes_of, const flbgpu_filter *offsets_of, flbgpu_dev_chunk *out, uint64_t n, uint64_t total) {
+    out->data = bytes_of->d_out.p; out->row_off = offsets_of->d_off.as<uint64_t>(); out->n = n; out->bytes = total;
 }
+void set_out(flbgpu_filter *f, flbgpu_dev_chunk *out, uint64_t n, uint64_t total) { set_out(f, f, out, n, total); }
 
 // the most blocks a lane-per-record launch gets (lane_rows.inc): 65536.  The test switch FLBGPU_LANE_MAX_BLOCKS=<1 ... 65536>, read
 // once per process, lowers it, so that the row loops' further trips are met with a thousand records; anything else leaves 65536.

@@ -60,5 +60,7 @@ inline bool scan_lengths(flbgpu_filter *f, hipStream_t st, const uint32_t *len, 
 }
 // the output chunk of a call that emitted: f->d_out under the offsets of f->d_off
 void set_out(flbgpu_filter *f, flbgpu_dev_chunk *out, uint64_t n, uint64_t total);
+// ... of a pair that ran as one pass: the bytes are one filter's d_out, the offsets the other's d_off
+void set_out(const flbgpu_filter *bytes_of, const flbgpu_filter *offsets_of, flbgpu_dev_chunk *out, uint64_t n, uint64_t total);
 
 }  // namespace flbgpu

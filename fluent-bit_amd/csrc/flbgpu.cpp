@@ -13,7 +13,7 @@
 #include <chrono>
 #include <mutex>
 #include <thread>
-#include "host_int.hpp"
+#include "filter_host.hpp"
 #include "grep_lane.hpp"
 #include "perm.hpp"
 
@@ -801,9 +801,9 @@ bool flbgpu::parse_ra(const char *pat, DevKey &k, std::string &why) {
 
 // ------------------------------------------------------------------------------------------ filters
 bool filter_common_init(flbgpu_filter *f) {
-    HIPOK(hipStreamCreate(&f->stream));
-    HIPOK(hipEventCreate(&f->ev0));
-    HIPOK(hipEventCreate(&f->ev1));
+    HIPOK(hipStreamCreate(&f->stream.h));
+    HIPOK(hipEventCreate(&f->ev0.h));
+    HIPOK(hipEventCreate(&f->ev1.h));
     return true;
 }
 
@@ -931,7 +931,14 @@ extern "C" flbgpu_filter *flbgpu_filter_parser_create(const char *key_name, int 
     return f;
 }
 
-bool flbgpu::compile_rule(const std::string &ra_field, const char *pattern, GrepRule &r, std::vector<TableBlob *> &blobs, std::string &why, bool *nonregular) {
+bool flbgpu::upload_rule(const rx::Program &prog, GrepRule &r, std::vector<std::unique_ptr<TableBlob>> &blobs) {
+    blobs.emplace_back(new TableBlob());
+    TableBlob &b1 = *blobs.back();
+    blobs.emplace_back(new TableBlob());
+    return upload_dfa(prog.ascii, b1, r.dfa) && upload_utf8(prog, *blobs.back(), r.utf8);
+}
+
+bool flbgpu::compile_rule(const std::string &ra_field, const char *pattern, GrepRule &r, std::vector<std::unique_ptr<TableBlob>> &blobs, std::string &why, bool *nonregular) {
     std::string w2;
     if (!parse_ra(ra_field.c_str(), r.key, w2)) { why = "invalid record accessor? '" + ra_field + "': " + w2; return false; }
     const char *ps, *pe;
@@ -944,10 +951,7 @@ bool flbgpu::compile_rule(const std::string &ra_field, const char *pattern, Grep
         if (nonregular) *nonregular = prog.nonregular;
         return false;
     }
-    auto *b1 = new TableBlob(), *b2 = new TableBlob();
-    blobs.push_back(b1);
-    blobs.push_back(b2);
-    if (!upload_dfa(prog.ascii, *b1, r.dfa) || !upload_utf8(prog, *b2, r.utf8)) { why = flbgpu_last_error(); return false; }
+    if (!upload_rule(prog, r, blobs)) { why = flbgpu_last_error(); return false; }
     return true;
 }
 
@@ -1101,8 +1105,19 @@ extern "C" void flbgpu_parser_destroy(flbgpu_parser *p) {
 }
 
 // ------------------------------------------------------------------------------------------ run (device level)
-struct MiscWords { unsigned long long first_bad; unsigned long long max_row; unsigned long long counts[18]; unsigned int ov_count; unsigned int kept_count; };      // counts[16], [17]: ParserMatchArgs::len_stat
+struct MiscWords { unsigned long long first_bad; unsigned long long max_row; unsigned long long counts[flbgpu::MW_N]; unsigned int ov_count; unsigned int kept_count; };      // counts: parser_words.hpp names the slots
 static const unsigned int OV_CAP = 1u << 16;      // (record, index) pairs of FParserCfg's side list
+// a call's counter block: f->d_misc on the device, its host mirror in f->hp_misc and MISC_TAIL words behind the mirror -- page-locked,
+// so that the small copies are real asynchronous DMA transfers.  misc_tail(hm)[0] is the output size, [1 ..] are the fused pair's
+// (run_pair_fused: the counters k_pg_emit raises, read after the others)
+enum { MISC_TAIL = 4 };
+static inline uint64_t *misc_tail(MiscWords *hm) { return (uint64_t *) (hm + 1); }
+struct MiscBlock { MiscWords *dm = nullptr, *hm = nullptr; uint64_t *total = nullptr; };
+static inline bool misc_words(flbgpu_filter *f, MiscBlock &b) {
+    if (!f->d_misc.ensure(sizeof(MiscWords)) || !f->hp_misc.ensure(sizeof(MiscWords) + MISC_TAIL * sizeof(uint64_t))) return false;
+    b.dm = f->d_misc.as<MiscWords>(); b.hm = f->hp_misc.as<MiscWords>(); b.total = misc_tail(b.hm);
+    return true;
+}
 
 // Pass 1 of filter_parser on a device chunk: every record decoded, located, matched and sized (locate / rx /
 // finish, the generic kernel for the records outside the fast shape).  On return out_len[r] (f->d_len) holds the
@@ -1177,7 +1192,7 @@ static inline bool spec_wanted(uint64_t n, uint64_t bytes) { return n <= SPEC_MA
 // the three-port ones again later (host_int.hpp Probe)
 static void note_fx5(flbgpu_filter *f, const MiscWords &hm, uint64_t n) {
     if (!f->last_fx5 || n < 64 || !f->parsers[0]->fx2b.ok) return;
-    if (hm.counts[9] * 64 > n) f->fx5.bad(); else f->fx5.good();
+    if (hm.counts[MW_SLOW] * 64 > n) f->fx5.bad(); else f->fx5.good();
 }
 // values the forward walk from boundary 0 does not settle take the reverse pass with tables in global memory: when that is the rule for
 // this pattern / this data, the phase kernels (tables in LDS) are the better choice for the next calls.  NOT after a launch that walked
@@ -1186,15 +1201,15 @@ static void note_fx5(flbgpu_filter *f, const MiscWords &hm, uint64_t n) {
 // it with the other tables.
 static void note_unsettled(flbgpu_filter *f, const MiscWords &hm, uint64_t n) {
     if (n < 64 || !(f->last_path & 1u)) return;
-    if (f->last_fx5 && f->parsers[0]->fx2b.ok && hm.counts[9] * 64 > n) return;
-    if (hm.counts[9] * 8 > n || hm.counts[10] * 4 > n) f->tile.bad(); else f->tile.good();
+    if (f->last_fx5 && f->parsers[0]->fx2b.ok && hm.counts[MW_SLOW] * 64 > n) return;
+    if (hm.counts[MW_SLOW] * 8 > n || hm.counts[MW_NEEDLOC] * 4 > n) f->tile.bad(); else f->tile.good();
 }
-// The register kernel's walk is position-synchronous: a wave steps as far as its longest record.  counts[16] / counts[17] = what the walk
+// The register kernel's walk is position-synchronous: a wave steps as far as its longest record.  counts[MW_LEN_STEPS] / counts[MW_LEN_BYTES] = what the walk
 // steps through in chunk order / what the rows hold (dev.hpp ParserMatchArgs::len_stat, perm.hpp): when the lines of this data differ
 // that much in length, the next calls walk the rows in the order of their lengths (kernels_perm.hip); back when they no longer do.
 static void note_lengths(flbgpu_filter *f, const MiscWords &hm) {
-    if (hm.counts[17] == 0) return;
-    const double ratio = (double) hm.counts[16] / (double) hm.counts[17];
+    if (hm.counts[MW_LEN_BYTES] == 0) return;
+    const double ratio = (double) hm.counts[MW_LEN_STEPS] / (double) hm.counts[MW_LEN_BYTES];
     if (ratio > 1.35) f->sort_rows = true;
     else if (ratio < 1.15) f->sort_rows = false;
 }
@@ -1202,7 +1217,45 @@ static bool ahead_counters_ok(flbgpu_filter *f, const MiscWords &hm, uint64_t n)
     note_lengths(f, hm);
     note_fx5(f, hm, n);
     note_unsettled(f, hm, n);
-    return hm.counts[8] == 0 && hm.counts[2] == 0 && hm.first_bad >= n;
+    return hm.counts[MW_FINISH] == 0 && hm.counts[MW_GENERIC] == 0 && hm.first_bad >= n;
+}
+
+// what the host matcher did: searches that ended on the backtrack budget, values searched, records not taken (flbgpu_filter_host_rules)
+struct HostTally {
+    uint64_t over = 0, vals = 0, unhandled = 0;
+    void operator+=(const HostTally &t) { over += t.over; vals += t.vals; unhandled += t.unhandled; }
+    void add_to(flbgpu_filter *f) const { f->host_budget_over += over; f->host_values += vals; f->host_unhandled += unhandled; }
+};
+
+// The row loop of a host parser: hp's capture search on the value of every RF_CAND row of info ([3][n]: flags, value offset, value length;
+// hd / off: the chunk on the host) that is no longer than vlen_max; store(r, flags, value, value offset, beg, end) takes the captures
+// of a row that matched, generic(r, flags) says whether a RF_GENERIC row counts as not taken.
+template <class Generic, class Store>
+static HostTally host_match_rows(const flbgpu_parser *hp, std::vector<uint32_t> &info, const uint8_t *hd, const std::vector<uint64_t> &off, uint64_t total_bytes,
+                                 uint32_t vlen_max, Generic generic, Store store) {
+    const uint64_t n = info.size() / 3;
+    std::atomic<uint64_t> over{0}, vals{0}, unhandled{0};
+    const int ng = rx::bt_ngroups(hp->bt);
+    parallel_rows(n, [&](uint64_t a, uint64_t b) {
+        std::vector<int> beg((size_t) ng + 1), end((size_t) ng + 1);
+        uint64_t ov = 0, nv = 0, un = 0;
+        for (uint64_t r = a; r < b; r++) {
+            const uint32_t fl = info[r];
+            if (fl & RF_GENERIC) { if (generic(r, fl)) un++; continue; }
+            if (!(fl & RF_CAND)) continue;
+            const uint32_t vo = info[(size_t) n + r], vlen = info[2 * (size_t) n + r];
+            if (off[r] + vo + (uint64_t) vlen > total_bytes || vlen > vlen_max) continue;
+            const uint8_t *val = hd + off[r] + vo;
+            const int res = rx::bt_search(hp->bt, val, (int) vlen, beg.data(), end.data());
+            nv++;
+            if (res == -4) ov++;
+            if (res > 0) store(r, fl, val, vo, beg.data(), end.data());
+        }
+        over += ov; vals += nv; unhandled += un;
+    });
+    HostTally t;
+    t.over = over.load(); t.vals = vals.load(); t.unhandled = unhandled.load();
+    return t;
 }
 
 // k_parser_rx's part for a host parser: the capture search of parser 0 on the values k_parser_locate found, by the backtracking
@@ -1219,42 +1272,25 @@ static bool host_parser_rx(flbgpu_filter *f, const flbgpu_dev_chunk *in, const P
     const uint8_t *hd = nullptr;
     if (!host_chunk(in, st, copy, &hd, off)) { set_err("filter_parser: copying the chunk back for the host parser failed"); return false; }
     std::vector<uint32_t> caps((size_t) ncap * n, 0u), tbuf((size_t) TBUF_WORDS * n, 0u);
-    std::atomic<uint64_t> over{0}, vals{0}, unhandled{0};
-    const uint64_t total_bytes = in->bytes;
-    const int ng = rx::bt_ngroups(hp->bt);
-    parallel_rows(n, [&](uint64_t a, uint64_t b) {
-        std::vector<int> beg((size_t) ng + 1), end((size_t) ng + 1);
-        uint64_t ov = 0, nv = 0, un = 0;
-        for (uint64_t r = a; r < b; r++) {
-            uint32_t fl = info[r];
-            if (fl & RF_GENERIC) { info[r] = fl & ~(uint32_t) RF_GENERIC; un++; continue; }     // (duplicate Key_Name entries, a value of 64 KB or more: not taken)
-            if (!(fl & RF_CAND)) continue;
-            const uint32_t vo = info[(size_t) n + r], vlen = info[2 * (size_t) n + r];
-            if (off[r] + vo + (uint64_t) vlen > total_bytes) continue;
-            const uint8_t *val = hd + off[r] + vo;
-            const int res = rx::bt_search(hp->bt, val, (int) vlen, beg.data(), end.data());
-            nv++;
-            if (res == -4) ov++;
-            if (res <= 0) continue;
-            for (int q = 0; q < d.nfields; q++) {
-                const int g = d.field_group[q];
-                caps[(size_t) (2 * q) * n + r] = beg[(size_t) g] >= 0 ? (uint32_t) beg[(size_t) g] : CAP_UNSET;
-                caps[(size_t) (2 * q + 1) * n + r] = end[(size_t) g] >= 0 ? (uint32_t) end[(size_t) g] : CAP_UNSET;
-            }
-            info[r] = fl | RF_RXOK;
-            if (d.time_field >= 0) {
-                const uint32_t tb = caps[(size_t) (2 * d.time_field) * n + r], te = caps[(size_t) (2 * d.time_field + 1) * n + r];
-                if (tb != CAP_UNSET && te != CAP_UNSET && te >= tb && te - tb <= 4 * TBUF_WORDS) {
-                    uint8_t tx[4 * TBUF_WORDS];
-                    memset(tx, 0, sizeof(tx));
-                    memcpy(tx, val + tb, te - tb);
-                    for (int k = 0; k < TBUF_WORDS; k++) { uint32_t w; memcpy(&w, tx + 4 * k, 4); tbuf[(size_t) k * n + r] = w; }
-                }
+    // a value of any length is searched; a RF_GENERIC row (duplicate Key_Name entries, a value of 64 KB or more) is not taken and counted
+    host_match_rows(hp, info, hd, off, in->bytes, 0xFFFFFFFFu, [&](uint64_t r, uint32_t fl) { info[r] = fl & ~(uint32_t) RF_GENERIC; return true; },
+                    [&](uint64_t r, uint32_t fl, const uint8_t *val, uint32_t, const int *beg, const int *end) {
+        for (int q = 0; q < d.nfields; q++) {
+            const int g = d.field_group[q];
+            caps[(size_t) (2 * q) * n + r] = beg[g] >= 0 ? (uint32_t) beg[g] : CAP_UNSET;
+            caps[(size_t) (2 * q + 1) * n + r] = end[g] >= 0 ? (uint32_t) end[g] : CAP_UNSET;
+        }
+        info[r] = fl | RF_RXOK;
+        if (d.time_field >= 0) {
+            const uint32_t tb = caps[(size_t) (2 * d.time_field) * n + r], te = caps[(size_t) (2 * d.time_field + 1) * n + r];
+            if (tb != CAP_UNSET && te != CAP_UNSET && te >= tb && te - tb <= 4 * TBUF_WORDS) {
+                uint8_t tx[4 * TBUF_WORDS];
+                memset(tx, 0, sizeof(tx));
+                memcpy(tx, val + tb, te - tb);
+                for (int k = 0; k < TBUF_WORDS; k++) { uint32_t w; memcpy(&w, tx + 4 * k, 4); tbuf[(size_t) k * n + r] = w; }
             }
         }
-        over += ov; vals += nv; unhandled += un;
-    });
-    f->host_budget_over += over.load(); f->host_values += vals.load(); f->host_unhandled += unhandled.load();
+    }).add_to(f);
     HIPOK(hipMemcpyAsync(ma.caps, caps.data(), caps.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     HIPOK(hipMemcpyAsync(ma.info, info.data(), (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice, st));
     if (ma.tbuf) HIPOK(hipMemcpyAsync(ma.tbuf, tbuf.data(), tbuf.size() * sizeof(uint32_t), hipMemcpyHostToDevice, st));
@@ -1273,44 +1309,31 @@ static bool host_list_rx(flbgpu_filter *f, const flbgpu_dev_chunk *in, ParserMat
     std::vector<uint64_t> off;
     const uint8_t *hd = nullptr;
     if (!host_chunk(in, st, copy, &hd, off)) { set_err("filter_parser: copying the chunk back for the host parsers failed"); return false; }
-    const uint64_t total_bytes = in->bytes;
     int slot = 0;
-    std::atomic<uint64_t> over{0}, vals{0}, unhandled{0};
+    HostTally tally;
     for (size_t q = 0; q < f->parsers.size(); q++) {
         const flbgpu_parser *hp = f->parsers[q];
         if (!hp->bt) continue;
         const DevParser &d = hp->dev;
-        const int ncap = 2 * d.nfields, ng = rx::bt_ngroups(hp->bt);
-        std::vector<uint32_t> res((size_t) (1 + ncap) * n, 0u);
+        std::vector<uint32_t> res((size_t) (1 + 2 * d.nfields) * n, 0u);
         const bool first = slot == 0;
-        parallel_rows(n, [&](uint64_t a, uint64_t b) {
-            std::vector<int> beg((size_t) ng + 1), end((size_t) ng + 1);
-            uint64_t ov = 0, nv = 0, un = 0;
-            for (uint64_t r = a; r < b; r++) {
-                const uint32_t fl = info[r];
-                if (fl & RF_GENERIC) { if (first) un++; continue; }      // (duplicate Key_Name entries: the value was not located as one -- the matcher's answer is "no")
-                if (!(fl & RF_CAND)) continue;
-                const uint32_t vo = info[(size_t) n + r], vlen = info[2 * (size_t) n + r];
-                if (off[r] + vo + (uint64_t) vlen > total_bytes || vlen > 0x7FFFFFF0u) continue;
-                const int rr = rx::bt_search(hp->bt, hd + off[r] + vo, (int) vlen, beg.data(), end.data());
-                nv++;
-                if (rr == -4) ov++;
-                if (rr <= 0) continue;
-                res[r] = vo + 1;
-                for (int k = 0; k < d.nfields; k++) {
-                    const int g = d.field_group[k];
-                    res[(size_t) (1 + 2 * k) * n + r] = beg[(size_t) g] >= 0 ? (uint32_t) beg[(size_t) g] : CAP_UNSET;
-                    res[(size_t) (2 + 2 * k) * n + r] = end[(size_t) g] >= 0 ? (uint32_t) end[(size_t) g] : CAP_UNSET;
-                }
+        // a value the matcher's int length cannot hold is not searched; a RF_GENERIC row (duplicate Key_Name entries: the value was not
+        // located as one -- the matcher's answer is "no") is counted once, with the first host parser
+        tally += host_match_rows(hp, info, hd, off, in->bytes, 0x7FFFFFF0u, [&](uint64_t, uint32_t) { return first; },
+                                 [&](uint64_t r, uint32_t, const uint8_t *, uint32_t vo, const int *beg, const int *end) {
+            res[r] = vo + 1;
+            for (int k = 0; k < d.nfields; k++) {
+                const int g = d.field_group[k];
+                res[(size_t) (1 + 2 * k) * n + r] = beg[g] >= 0 ? (uint32_t) beg[g] : CAP_UNSET;
+                res[(size_t) (2 + 2 * k) * n + r] = end[g] >= 0 ? (uint32_t) end[g] : CAP_UNSET;
             }
-            over += ov; vals += nv; unhandled += un;
         });
         if (!f->d_hres[slot].ensure(res.size() * sizeof(uint32_t))) return false;
         HIPOK(hipMemcpy(f->d_hres[slot].p, res.data(), res.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
         ma.host_res[slot] = f->d_hres[slot].as<uint32_t>();
         slot++;
     }
-    f->host_budget_over += over.load(); f->host_values += vals.load(); f->host_unhandled += unhandled.load();
+    tally.add_to(f);
     for (uint64_t r = 0; r < n; r++) if (info[r] & RF_CAND) info[r] |= RF_GENERIC;
     HIPOK(hipMemcpy(ma.info, info.data(), (size_t) n * sizeof(uint32_t), hipMemcpyHostToDevice));
     return true;
@@ -1319,12 +1342,9 @@ static bool host_list_rx(flbgpu_filter *f, const flbgpu_dev_chunk *in, ParserMat
 static bool parser_size_pass(flbgpu_filter *f, const flbgpu_dev_chunk *in, hipStream_t st, MiscWords **dm_out, MiscWords **hm_out, uint64_t *n_valid,
                              PairCtx *pair = nullptr, bool *ahead = nullptr) {
     uint64_t n = in->n;
-    if (!f->d_misc.ensure(sizeof(MiscWords))) return false;
-    MiscWords *dm = f->d_misc.as<MiscWords>();
-    // host mirror of the counters + the output size, page-locked so that the small copies are real
-    // asynchronous DMA transfers
-    if (!f->hp_misc.ensure(sizeof(MiscWords) + 4 * sizeof(uint64_t))) return false;
-    MiscWords &hm = *f->hp_misc.as<MiscWords>();
+    MiscBlock mb;
+    if (!misc_words(f, mb)) return false;
+    MiscWords *dm = mb.dm, &hm = *mb.hm;
     *dm_out = dm; *hm_out = &hm;
     const uint64_t *row_off = in->row_off;
     const uint8_t *data = (const uint8_t *) in->data;
@@ -1439,7 +1459,7 @@ static bool parser_size_pass(flbgpu_filter *f, const flbgpu_dev_chunk *in, hipSt
     ma.chk_len = chk_len; ma.chk_nfa_off = chk_len; ma.lds_bytes = lds_bytes; ma.caps_lds_off = tab_bytes; ma.caps_in_lds = caps_bytes ? 1 : 0;
     ma.lds_total = tab_bytes + caps_bytes; ma.debug_skip = getenv("FLBGPU_DEBUG_SKIP") ? (uint32_t) atoi(getenv("FLBGPU_DEBUG_SKIP")) : 0; ma.first_bad = &dm->first_bad; ma.counts = dm->counts;
     ma.bytes = in->bytes;
-    ma.pg = nullptr; ma.pg_lds_off = 0; ma.pg_keep_len = nullptr; ma.self = nullptr; ma.desc = nullptr; ma.dstride = 0; ma.fix_first = 0; ma.fix_list = nullptr; ma.fix_count = &dm->counts[12]; ma.tail_buf = nullptr; ma.tail_start = 0; ma.stage_lds_off = 0; ma.stage_bytes = 0; ma.stage_nbuf = 0; ma.trace = nullptr; ma.trace_iters = 0;
+    ma.pg = nullptr; ma.pg_lds_off = 0; ma.pg_keep_len = nullptr; ma.self = nullptr; ma.desc = nullptr; ma.dstride = 0; ma.fix_first = 0; ma.fix_list = nullptr; ma.fix_count = &dm->counts[MW_FIX_COUNT]; ma.tail_buf = nullptr; ma.tail_start = 0; ma.stage_lds_off = 0; ma.stage_bytes = 0; ma.stage_nbuf = 0; ma.trace = nullptr; ma.trace_iters = 0;
     for (auto &hr : ma.host_res) hr = nullptr;
     ma.perm = nullptr; ma.len_stat = nullptr;
     ma.tile_lds_off = 0; ma.tile_wave_bytes = tile_wave_bytes; ma.use_fx2 = use_fx2 ? (fx.pair_bias == 2 ? 5 : fx.pair_bias ? 4 : 3) : 0;
@@ -1558,7 +1578,7 @@ static bool parser_size_pass(flbgpu_filter *f, const flbgpu_dev_chunk *in, hipSt
         { ProfScope ps(f, st, "k_pjson_size"); launch_pjson_size(ma, cus, st); }
         HIPOK(hipMemcpyAsync(&hm, dm, sizeof(hm), hipMemcpyDeviceToHost, st));
         HIPOK(hipStreamSynchronize(st));
-        if (hm.counts[2] > 0) {
+        if (hm.counts[MW_GENERIC] > 0) {
             if (f->pcfg.nparsers > 1) { if (!run_generic()) return false; }      // the other parsers of the list get their turn
             else { ProfScope ps(f, st, "k_pjson_size_generic"); launch_pjson_size_generic(ma, st); }
         }
@@ -1606,12 +1626,12 @@ static bool parser_size_pass(flbgpu_filter *f, const flbgpu_dev_chunk *in, hipSt
         // FLBGPU_SORT_ROWS=0 / 1: never / always, for measurements); a call launched ahead of its sizes keeps the chunk's order
         if (!tile_in_lds && ma.fix_list && n >= 4096) {
             static const int sort_env = getenv("FLBGPU_SORT_ROWS") ? atoi(getenv("FLBGPU_SORT_ROWS")) : -1;
-            ma.len_stat = &dm->counts[16];
+            ma.len_stat = &dm->counts[MW_LEN_STEPS];
             if ((sort_env >= 0 ? sort_env != 0 : f->sort_rows) && !g_spec.on) {
                 const size_t wb = row_perm_work_bytes(n);
                 if (f->d_perm.ensure(n * sizeof(uint32_t)) && f->d_permwork.ensure(wb)) {
                     ProfScope ps(f, st, "k_row_perm");
-                    if (!launch_row_perm(row_off, n, f->d_perm.as<uint32_t>(), f->d_permwork.p, wb, &dm->counts[16], st)) { set_err("filter_parser: ordering the rows by length failed"); return false; }
+                    if (!launch_row_perm(row_off, n, f->d_perm.as<uint32_t>(), f->d_permwork.p, wb, &dm->counts[MW_LEN_STEPS], st)) { set_err("filter_parser: ordering the rows by length failed"); return false; }
                     ma.perm = f->d_perm.as<uint32_t>();
                     ma.stage_nbuf = 0;
                     f->last_path |= 16u;
@@ -1658,7 +1678,7 @@ static bool parser_size_pass(flbgpu_filter *f, const flbgpu_dev_chunk *in, hipSt
         if (d_trace && !(ma.trace_iters >> 31)) trace_out();
         HIPOK(hipMemcpyAsync(&hm, dm, sizeof(hm), hipMemcpyDeviceToHost, st));
         HIPOK(hipStreamSynchronize(st));
-        if (f->last_fx5 && n >= 64 && f->parsers[0]->fx2b.ok && hm.counts[9] * 64 > n && !d_trace) {
+        if (f->last_fx5 && n >= 64 && f->parsers[0]->fx2b.ok && hm.counts[MW_SLOW] * 64 > n && !d_trace) {
             // The three-port tables hand more than one row in 64 of THIS chunk on (a try of the set-aside tables on data that has not
             // changed, or the first chunk of such data): the kernels behind the walk would now pay for every such row (6.1 ms of
             // k_parser_generic on bench.py's mixed shapes, where the pass itself takes 0.9) -- the call again from the top instead, with the
@@ -1667,10 +1687,10 @@ static bool parser_size_pass(flbgpu_filter *f, const flbgpu_dev_chunk *in, hipSt
             f->again = true;
             return false;
         }
-        if (!tile_in_lds && hm.counts[10] > 0) {
+        if (!tile_in_lds && hm.counts[MW_NEEDLOC] > 0) {
             // rows the call-free kernel only flagged (another layout, the last records of the chunk): the same pass with the
             // general locate, guarded loads and the reverse-pass fallback, for those rows
-            ma.fix_first = hm.counts[11] <= n ? n - hm.counts[11] : 0;
+            ma.fix_first = hm.counts[MW_FIX_SPAN] <= n ? n - hm.counts[MW_FIX_SPAN] : 0;
             uint64_t fix_blocks = ((n - (ma.fix_first & ~63ull)) + (uint64_t) rx_threads - 1) / (uint64_t) rx_threads;
             if (fix_blocks > (uint64_t) grid) fix_blocks = (uint64_t) grid;
             if (ma.fix_list) fix_blocks = (uint64_t) grid;                       // the same shape: wave w takes what wave w listed
@@ -1683,13 +1703,13 @@ static bool parser_size_pass(flbgpu_filter *f, const flbgpu_dev_chunk *in, hipSt
         note_lengths(f, hm);
         note_fx5(f, hm, n);
         note_unsettled(f, hm, n);
-        if (hm.counts[8] > 0) {
+        if (hm.counts[MW_FINISH] > 0) {
             // rows whose time text needs the strptime interpreter, sizes that depend on the record's bytes, ...
             { ProfScope ps(f, st, "k_parser_finish"); launch_parser_finish(ma, cus, st); }
             HIPOK(hipMemcpyAsync(&hm, dm, sizeof(hm), hipMemcpyDeviceToHost, st));
             HIPOK(hipStreamSynchronize(st));
         }
-        if (hm.counts[2] > 0 && !run_generic()) return false;
+        if (hm.counts[MW_GENERIC] > 0 && !run_generic()) return false;
     }
     else {
         { ProfScope ps(f, st, "k_parser_locate"); launch_parser_locate(ma, cus, st); }
@@ -1697,7 +1717,7 @@ static bool parser_size_pass(flbgpu_filter *f, const flbgpu_dev_chunk *in, hipSt
         { ProfScope ps(f, st, "k_parser_finish"); launch_parser_finish(ma, cus, st); }
         HIPOK(hipMemcpyAsync(&hm, dm, sizeof(hm), hipMemcpyDeviceToHost, st));
         HIPOK(hipStreamSynchronize(st));
-        if (hm.counts[2] > 0 && !run_generic()) return false;
+        if (hm.counts[MW_GENERIC] > 0 && !run_generic()) return false;
     }
     if (hm.first_bad < n) n = hm.first_bad;                 // the decoder loop ends at the first bad record
     *n_valid = n;
@@ -1718,6 +1738,17 @@ static void fill_emit_cfg(const flbgpu_filter *f, EmitCfg &ec) {
     ec.nfields = d.nfields; ec.nregs_minus1 = d.nregs_minus1; ec.ok = 1;
 }
 
+// k_parser_emit's arguments: the first n rows of `in` under the size pass's columns into f->d_out; out_cap: ParserEmitArgs::out_cap
+static ParserEmitArgs fill_emit_args(const flbgpu_filter *f, const flbgpu_dev_chunk *in, uint64_t n, uint64_t out_cap) {
+    ParserEmitArgs ea;
+    ea.data = (const uint8_t *) in->data; ea.row_off = in->row_off; ea.n = n; ea.cfg = f->pcfg; ea.parsers = f->d_parsers.as<DevParser>();
+    ea.n_cols = in->n; ea.info = f->d_info.as<uint32_t>(); ea.caps = f->d_caps.as<uint32_t>(); ea.caps_stride = f->caps_stride;
+    ea.null_mask = f->d_null.as<uint64_t>(); ea.out_len = f->d_len.as<uint32_t>(); ea.out_off = f->d_off.as<uint64_t>();
+    ea.out = f->d_out.as<uint8_t>(); ea.bytes = in->bytes; ea.out_cap = out_cap;
+    fill_emit_cfg(f, ea.ec);
+    return ea;
+}
+
 static bool run_parser_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_dev_chunk *out, hipStream_t st, int *ret) {
     uint64_t n = in->n;
     *ret = FLBGPU_FILTER_NOTOUCH;
@@ -1730,7 +1761,7 @@ static bool run_parser_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_
         return false;
     }
     MiscWords &hm = *hmp;
-    uint64_t &total = *(uint64_t *) (f->hp_misc.as<uint8_t>() + sizeof(MiscWords));
+    uint64_t &total = *misc_tail(hmp);
     const uint64_t *row_off = in->row_off;
     const uint8_t *data = (const uint8_t *) in->data;
     const int cus = g_cus > 0 ? g_cus : 256;
@@ -1759,8 +1790,8 @@ static bool run_parser_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_
         dca.e.n_cols = in->n; dca.e.info = f->d_info.as<uint32_t>(); dca.e.caps = f->d_caps.as<uint32_t>(); dca.e.caps_stride = f->caps_stride;
         dca.e.null_mask = f->d_null.as<uint64_t>(); dca.e.out_len = f->d_len.as<uint32_t>(); dca.e.out_off = nullptr; dca.e.out = nullptr; dca.e.bytes = in->bytes;
         dca.info_w = f->d_info.as<uint32_t>(); dca.out_len_w = f->d_len.as<uint32_t>(); dca.scratch = f->d_dec.as<uint8_t>(); dca.cap = (uint32_t) cap;
-        dca.mode = 0; dca.err = &dm->counts[10]; dca.ndec = &dm->counts[11];
-        HIPOK(hipMemsetAsync(&dm->counts[10], 0, 2 * sizeof(unsigned long long), st));
+        dca.mode = 0; dca.err = &dm->counts[MW_DEC_OVER]; dca.ndec = &dm->counts[MW_DEC_ROWS];
+        HIPOK(hipMemsetAsync(&dm->counts[MW_DEC_OVER], 0, 2 * sizeof(unsigned long long), st));
         { ProfScope ps(f, st, "k_parser_dec_size"); launch_parser_dec(dca, dec_blocks, st); }
         f->dec_launch[0] = lanes; f->dec_launch[1] = cap; f->dec_launch[4]++;
         return true;
@@ -1773,77 +1804,71 @@ static bool run_parser_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_
         if (!dec_size((uint64_t) hm.max_row * 3 + 4096)) return false;
     }
     // write offsets + the number of emitted records (what flb_mp_count_log_records would report) in one pass
-    { ProfScope ps(f, st, "k_scan"); launch_scan(f->d_len.as<uint32_t>(), n, f->d_scan_tmp.as<uint64_t>(), f->d_off.as<uint64_t>(), st, &dm->counts[1]); }
+    auto scan = [&]() { ProfScope ps(f, st, "k_scan"); launch_scan(f->d_len.as<uint32_t>(), n, f->d_scan_tmp.as<uint64_t>(), f->d_off.as<uint64_t>(), st, &dm->counts[MW_EMITTED]); };
+    // ... and what it found on the host: the size behind the offsets, the counters, one wait
+    auto sizes_back = [&]() -> bool {
+        HIPOK(hipMemcpyAsync(&total, f->d_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIPOK(hipMemcpyAsync(&hm, dm, sizeof(hm), hipMemcpyDeviceToHost, st));
+        HIPOK(hipStreamSynchronize(st));
+        return true;
+    };
+    scan();
     total = 0;
     if (ahead) {
         // launched ahead (SpecCall): the writer with room for the usual output, counters + size + (host-level call) the output itself
         // written to page-locked memory by the device, ONE wait
         if (!f->d_out.ensure(in->bytes * 2 + n * 64 + 65536 + 16)) return false;
-        ParserEmitArgs ea;
-        ea.data = data; ea.row_off = row_off; ea.n = n; ea.cfg = f->pcfg; ea.parsers = f->d_parsers.as<DevParser>();
-        ea.n_cols = in->n; ea.info = f->d_info.as<uint32_t>(); ea.caps = f->d_caps.as<uint32_t>(); ea.caps_stride = f->caps_stride;
-        ea.null_mask = f->d_null.as<uint64_t>(); ea.out_len = f->d_len.as<uint32_t>(); ea.out_off = f->d_off.as<uint64_t>();
-        ea.out = f->d_out.as<uint8_t>(); ea.bytes = in->bytes; ea.out_cap = f->d_out.cap - 16;
-        fill_emit_cfg(f, ea.ec);
+        const ParserEmitArgs ea = fill_emit_args(f, in, n, f->d_out.cap - 16);
         { ProfScope ps(f, st, "k_parser_emit"); launch_parser_emit(ea, cus, st); }
         uint8_t *sink = g_spec.last ? g_spec.sink : nullptr;
         launch_finish_to_host(ea.out, ea.out_cap, ea.out_off + n, sink, g_spec.sink_cap, dm, &hm, (uint32_t) sizeof(hm), &total, st);
         HIPOK(hipStreamSynchronize(st));
-        if (!ahead_counters_ok(f, hm, n) || hm.counts[3] > 0 || hm.ov_count > OV_CAP || total > ea.out_cap) {
+        if (!ahead_counters_ok(f, hm, n) || hm.counts[MW_EXACT] > 0 || hm.ov_count > OV_CAP || total > ea.out_cap) {
             SpecOff usual;
             return run_parser_dev(f, in, out, st, ret);
         }
-        f->last_in = hm.counts[0];
+        f->last_in = hm.counts[MW_DECODED];
         if (total == 0) return true;
-        out->data = f->d_out.p; out->row_off = f->d_off.as<uint64_t>(); out->n = n; out->bytes = total;
-        f->last_out = hm.counts[1] - (hm.counts[14] < hm.counts[1] ? hm.counts[14] : hm.counts[1]);   // (see below)
+        set_out(f, out, n, total);
+        f->last_out = hm.counts[MW_EMITTED] - (hm.counts[MW_TIME_MARKER] < hm.counts[MW_EMITTED] ? hm.counts[MW_TIME_MARKER] : hm.counts[MW_EMITTED]);   // (see below)
         if (sink && total <= g_spec.sink_cap) g_spec.sunk = true;
         *ret = FLBGPU_FILTER_MODIFIED;
         return true;
     }
-    HIPOK(hipMemcpyAsync(&total, f->d_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    HIPOK(hipMemcpyAsync(&hm, dm, sizeof(hm), hipMemcpyDeviceToHost, st));
-    HIPOK(hipStreamSynchronize(st));
+    if (!sizes_back()) return false;
     // rows that outgrew the decoders' scratch: their sizes are not known yet, so neither `total` nor the offsets are -- the size pass
     // and the scan again with twice the room, until every row fits (or the room can no longer be had: the call fails, as before)
-    while (f->has_decoders && hm.counts[10] > 0) {
-        f->dec_launch[3] += hm.counts[10];
-        const unsigned long long over = hm.counts[10];
+    while (f->has_decoders && hm.counts[MW_DEC_OVER] > 0) {
+        f->dec_launch[3] += hm.counts[MW_DEC_OVER];
+        const unsigned long long over = hm.counts[MW_DEC_OVER];
         if (!dec_size(dec_cap * 2)) { set_err("filter_parser: a decoded field outgrew the decoders' scratch (%llu records) and no larger one can be had", over); return false; }
-        HIPOK(hipMemsetAsync(&dm->counts[1], 0, sizeof(unsigned long long), st));
-        { ProfScope ps(f, st, "k_scan"); launch_scan(f->d_len.as<uint32_t>(), n, f->d_scan_tmp.as<uint64_t>(), f->d_off.as<uint64_t>(), st, &dm->counts[1]); }
-        HIPOK(hipMemcpyAsync(&total, f->d_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        HIPOK(hipMemcpyAsync(&hm, dm, sizeof(hm), hipMemcpyDeviceToHost, st));
-        HIPOK(hipStreamSynchronize(st));
+        HIPOK(hipMemsetAsync(&dm->counts[MW_EMITTED], 0, sizeof(unsigned long long), st));
+        scan();
+        if (!sizes_back()) return false;
     }
-    f->dec_launch[2] = f->has_decoders ? hm.counts[11] : 0;
-    f->last_in = hm.counts[0];
+    f->dec_launch[2] = f->has_decoders ? hm.counts[MW_DEC_ROWS] : 0;
+    f->last_in = hm.counts[MW_DECODED];
     if (hm.ov_count > OV_CAP) {
         set_err("filter_parser: more than %u parsed Key_Name entries at body map index 64 and up in one chunk", OV_CAP);
         return false;
     }
     if (total == 0) return true;                            // encoder produced nothing: NOTOUCH (+ error log)
     if (!f->d_out.ensure(total + 16)) return false;
-    ParserEmitArgs ea;
-    ea.data = data; ea.row_off = row_off; ea.n = n; ea.cfg = f->pcfg; ea.parsers = f->d_parsers.as<DevParser>();
-    ea.n_cols = in->n; ea.info = f->d_info.as<uint32_t>(); ea.caps = f->d_caps.as<uint32_t>(); ea.caps_stride = f->caps_stride;
-    ea.null_mask = f->d_null.as<uint64_t>(); ea.out_len = f->d_len.as<uint32_t>(); ea.out_off = f->d_off.as<uint64_t>();
-    ea.out = f->d_out.as<uint8_t>(); ea.bytes = in->bytes; ea.out_cap = 0;
-    fill_emit_cfg(f, ea.ec);
+    const ParserEmitArgs ea = fill_emit_args(f, in, n, 0);
     { ProfScope ps(f, st, "k_parser_emit"); launch_parser_emit(ea, cus, st); }
-    if (hm.counts[3] > 0) { ProfScope ps(f, st, "k_parser_emit_exact"); launch_parser_emit_exact(ea, st); }
-    if (f->has_decoders && hm.counts[11] > 0) {
+    if (hm.counts[MW_EXACT] > 0) { ProfScope ps(f, st, "k_parser_emit_exact"); launch_parser_emit_exact(ea, st); }
+    if (f->has_decoders && hm.counts[MW_DEC_ROWS] > 0) {
         dca.e.out_off = ea.out_off; dca.e.out = ea.out; dca.mode = 1;
         { ProfScope ps(f, st, "k_parser_dec_emit"); launch_parser_dec(dca, dec_blocks, st); }
         HIPOK(hipMemcpyAsync(&hm, dm, sizeof(hm), hipMemcpyDeviceToHost, st));
     }
     HIPOK(hipStreamSynchronize(st));
-    if (f->has_decoders && hm.counts[10] > 0) { set_err("filter_parser: a decoded field outgrew the decoders' scratch (%llu records)", hm.counts[10]); return false; }
-    out->data = f->d_out.p; out->row_off = f->d_off.as<uint64_t>(); out->n = n; out->bytes = total;
+    if (f->has_decoders && hm.counts[MW_DEC_OVER] > 0) { set_err("filter_parser: a decoded field outgrew the decoders' scratch (%llu records)", hm.counts[MW_DEC_OVER]); return false; }
+    set_out(f, out, n, total);
     // rows with length 0 (dropped/skipped) remain as empty rows; a record whose PARSED time reads as a group marker to the decoder
     // (ff ff ff ff / fe: -1 s, -2 s, 2106-02-07 06:28:14 / :15) is written but not counted: flb_filter_do re-counts the filter's output
     // with the log event decoder (src/flb_filter.c:272, src/flb_mp.c:49-71), which hides it
-    f->last_out = hm.counts[1] - (hm.counts[14] < hm.counts[1] ? hm.counts[14] : hm.counts[1]);
+    f->last_out = hm.counts[MW_EMITTED] - (hm.counts[MW_TIME_MARKER] < hm.counts[MW_EMITTED] ? hm.counts[MW_TIME_MARKER] : hm.counts[MW_EMITTED]);
     *ret = FLBGPU_FILTER_MODIFIED;
     return true;
 }
@@ -1888,10 +1913,10 @@ static bool lane_geometry(const flbgpu_dev_chunk *in, MiscWords *dm, hipStream_t
     const uint64_t n = in->n, avg = in->bytes / n + 1;
     uint64_t R = 64, cap = (64 * avg * 3 / 2 + 512 + 15) & ~15ull;
     if (n >= 65536) {
-        HIPOK(hipMemsetAsync(&dm->counts[13], 0, 8, st));
-        launch_tile_max(in->row_off, n, 64, &dm->counts[13], st);
+        HIPOK(hipMemsetAsync(&dm->counts[MW_TILE_MAX], 0, 8, st));
+        launch_tile_max(in->row_off, n, 64, &dm->counts[MW_TILE_MAX], st);
         unsigned long long mx = 0;
-        HIPOK(hipMemcpyAsync(&mx, &dm->counts[13], 8, hipMemcpyDeviceToHost, st));
+        HIPOK(hipMemcpyAsync(&mx, &dm->counts[MW_TILE_MAX], 8, hipMemcpyDeviceToHost, st));
         HIPOK(hipStreamSynchronize(st));
         cap = (mx + 32 + 15) & ~15ull;
     }
@@ -1919,13 +1944,10 @@ static bool run_grep_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_de
     *ret = FLBGPU_FILTER_NOTOUCH;
     f->last_in = 0; f->last_out = 0;
     if (n == 0) return true;
-    if (!f->d_misc.ensure(sizeof(MiscWords))) return false;
-    MiscWords *dm = f->d_misc.as<MiscWords>();
-    // host mirror of the counters + the output size, page-locked so that the small copies are real
-    // asynchronous DMA transfers
-    if (!f->hp_misc.ensure(sizeof(MiscWords) + 4 * sizeof(uint64_t))) return false;
-    MiscWords &hm = *f->hp_misc.as<MiscWords>();
-    uint64_t &total = *(uint64_t *) (f->hp_misc.as<uint8_t>() + sizeof(MiscWords));
+    MiscBlock mb;
+    if (!misc_words(f, mb)) return false;
+    MiscWords *dm = mb.dm, &hm = *mb.hm;
+    uint64_t &total = *mb.total;
     memset(&hm, 0, sizeof(hm));
     hm.first_bad = ~0ull;
     HIPOK(hipMemcpyAsync(dm, &hm, sizeof(hm), hipMemcpyHostToDevice, st));
@@ -2048,7 +2070,7 @@ static bool run_grep_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_de
             HIPOK(hipMemsetAsync(f->d_units.p, 0, nunits * 8, st));
             la.off_out = f->d_off.as<uint64_t>(); la.out = f->d_out.as<uint8_t>(); la.out_cap = in->bytes;
             la.unit_state = f->d_units.as<unsigned long long>();
-            la.ticket = &dm->counts[12]; la.words = &dm->counts[10];
+            la.ticket = &dm->counts[MW_LANE_TICKET]; la.words = &dm->counts[MW_LANE_BYTES];
             static const bool lane_prof = getenv("FLBGPU_GREP_PROF") != nullptr;      // (measurement only: the kernel stamps its phases)
             ScopedDevBuf d_prof;
             if (lane_prof) { if (!d_prof.ensure(64)) return false; HIPOK(hipMemsetAsync(d_prof.p, 0, 64, st)); la.prof = d_prof.as<unsigned long long>(); }
@@ -2064,13 +2086,13 @@ static bool run_grep_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_de
                         (double) tot / (double) n, 100.0 * ph[0] / tot, 100.0 * ph[1] / tot, 100.0 * ph[2] / tot, 100.0 * ph[3] / tot, 100.0 * (ph[4] > ph[1] + ph[2] + ph[3] ? ph[4] - ph[1] - ph[2] - ph[3] : 0) / tot,
                         100.0 * ph[5] / tot, 100.0 * ph[6] / tot, la.text_cap, la.rows_per_tile);
             }
-            if (hm.counts[11]) { set_err("filter_grep: the one-pass kernel %s", (hm.counts[11] >> 32) ? "gave up waiting for the workgroups in front" : "found no room for its output"); return false; }
-            f->last_in = hm.counts[0];
-            f->last_out = hm.counts[0];
+            if (hm.counts[MW_LANE_FAIL]) { set_err("filter_grep: the one-pass kernel %s", (hm.counts[MW_LANE_FAIL] >> 32) ? "gave up waiting for the workgroups in front" : "found no room for its output"); return false; }
+            f->last_in = hm.counts[MW_DECODED];
+            f->last_out = hm.counts[MW_DECODED];
             if (hm.first_bad != ~0ull || trailing_garbage) return true;           // (as below: a decoder error anywhere and the filter answers NOTOUCH)
-            if (hm.counts[0] == hm.counts[1]) return true;
-            f->last_out = hm.counts[1];
-            out->data = f->d_out.p; out->row_off = f->d_off.as<uint64_t>(); out->n = n; out->bytes = hm.counts[10];
+            if (hm.counts[MW_DECODED] == hm.counts[MW_KEPT]) return true;
+            f->last_out = hm.counts[MW_KEPT];
+            set_out(f, out, n, hm.counts[MW_LANE_BYTES]);
             *ret = FLBGPU_FILTER_MODIFIED;
             return true;
         }
@@ -2093,15 +2115,15 @@ static bool run_grep_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_de
         HIPOK(hipMemcpyAsync(&total, f->d_off.as<uint64_t>() + n, sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     }
     HIPOK(hipStreamSynchronize(st));
-    f->last_in = hm.counts[0];
-    f->last_out = hm.counts[0];
+    f->last_in = hm.counts[MW_DECODED];
+    f->last_out = hm.counts[MW_DECODED];
     // Any decoder error (bad event shape, truncated or malformed msgpack) ends the reference's
     // loop with an error code: whatever was kept, the filter answers NOTOUCH
     // (plugins/filter_grep/grep.c:356-385).  "we keep everything" compares RECORD COUNTS, and
     // group markers are not records (old_size == new_size, :362-371).
     if (hm.first_bad != ~0ull || trailing_garbage) return true;
-    if (hm.counts[0] == hm.counts[1]) return true;
-    f->last_out = hm.counts[1];
+    if (hm.counts[MW_DECODED] == hm.counts[MW_KEPT]) return true;
+    f->last_out = hm.counts[MW_KEPT];
     if (ahead) {
         if (sink && total <= g_spec.sink_cap) g_spec.sunk = true;
     }
@@ -2113,7 +2135,7 @@ static bool run_grep_dev(flbgpu_filter *f, const flbgpu_dev_chunk *in, flbgpu_de
         { ProfScope ps(f, st, "k_gather"); launch_gather(ta, st); }
         HIPOK(hipStreamSynchronize(st));
     }
-    out->data = f->d_out.p; out->row_off = f->d_off.as<uint64_t>(); out->n = n; out->bytes = total;
+    set_out(f, out, n, total);
     *ret = FLBGPU_FILTER_MODIFIED;
     return true;
 }
@@ -2140,9 +2162,9 @@ static int run_grep_pair(flbgpu_filter *f, flbgpu_filter *f2, const flbgpu_dev_c
     if (!lane_rules(f, la.g, la, used)) return 0;
     const int own = la.nslots;
     if (!lane_rules(f2, la.g2, la, used)) return 0;
-    if (!f->d_misc.ensure(sizeof(MiscWords)) || !f->hp_misc.ensure(sizeof(MiscWords) + 4 * sizeof(uint64_t))) return 0;
-    MiscWords *dm = f->d_misc.as<MiscWords>();
-    MiscWords &hm = *f->hp_misc.as<MiscWords>();
+    MiscBlock mb;
+    if (!misc_words(f, mb)) return 0;
+    MiscWords *dm = mb.dm, &hm = *mb.hm;
     memset(&hm, 0, sizeof(hm));
     hm.first_bad = ~0ull;
     if (hipMemcpyAsync(dm, &hm, sizeof(hm), hipMemcpyHostToDevice, st) != hipSuccess) return 0;
@@ -2166,12 +2188,12 @@ static int run_grep_pair(flbgpu_filter *f, flbgpu_filter *f2, const flbgpu_dev_c
     if (hipMemsetAsync(f->d_units.p, 0, nunits * 8, st) != hipSuccess) return 0;
     la.off_out = f->d_off.as<uint64_t>(); la.out = f2->d_out.as<uint8_t>(); la.out_cap = in->bytes;
     la.unit_state = f->d_units.as<unsigned long long>();
-    la.ticket = &dm->counts[12]; la.words = &dm->counts[10];
+    la.ticket = &dm->counts[MW_LANE_TICKET]; la.words = &dm->counts[MW_LANE_BYTES];
     { ProfScope ps(f, st, "k_grep_lane(two instances)"); launch_grep_lane(la, g_cus > 0 ? g_cus : 256, st); }
     if (hipMemcpyAsync(&hm, dm, sizeof(hm), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return 0;
-    if (hm.counts[11]) return 0;
+    if (hm.counts[MW_LANE_FAIL]) return 0;
     f->calls++; f2->calls++;
-    const uint64_t dec = hm.counts[0], kept1 = hm.counts[1], kept2 = hm.counts[2], bytes1 = hm.counts[3], bytes2 = hm.counts[10];
+    const uint64_t dec = hm.counts[MW_DECODED], kept1 = hm.counts[MW_KEPT], kept2 = hm.counts[MW_KEPT2], bytes1 = hm.counts[MW_BYTES1], bytes2 = hm.counts[MW_LANE_BYTES];
     memset(s2, 0, 2 * sizeof(*s2));
     *out = *in;
     f->last_in = f->last_out = dec; f2->last_in = f2->last_out = dec;
@@ -2187,7 +2209,7 @@ static int run_grep_pair(flbgpu_filter *f, flbgpu_filter *f2, const flbgpu_dev_c
             memset(&s2[1], 0, sizeof(s2[1]));
             f2->last_in = f2->last_out = 0;
             memset(out, 0, sizeof(*out));
-            out->data = f2->d_out.p; out->row_off = f->d_off.as<uint64_t>(); out->n = n; out->bytes = 0;
+            set_out(f2, f, out, n, 0);
             return 1;
         }
         f2->last_in = f2->last_out = kept1;
@@ -2198,7 +2220,7 @@ static int run_grep_pair(flbgpu_filter *f, flbgpu_filter *f2, const flbgpu_dev_c
         f2->last_out = kept2;
         s2[1].ret = FLBGPU_FILTER_MODIFIED; s2[1].out_records = kept2; s2[1].out_bytes = bytes2;
     }
-    if (mod1 || mod2) { out->data = f2->d_out.p; out->row_off = f->d_off.as<uint64_t>(); out->n = n; out->bytes = bytes2; }
+    if (mod1 || mod2) set_out(f2, f, out, n, bytes2);
     return 1;
 }
 
@@ -2291,9 +2313,9 @@ static int run_pair_fused(flbgpu_filter *fp, flbgpu_filter *fg, const flbgpu_dev
         return -1;
     }
     MiscWords &hm = *hmp;
-    uint64_t &total = *(uint64_t *) (fp->hp_misc.as<uint8_t>() + sizeof(MiscWords));
-    // (counts[14]: a parsed time filter_grep's decoder would read as a group marker -- the unfused kernels restate that, the pair does not)
-    if (!ahead && (n == 0 || hm.counts[3] > 0 || hm.ov_count > 0 || hm.counts[14] > 0)) return 0;           // (records for k_parser_emit_exact: unfused)
+    uint64_t &total = *misc_tail(hmp);
+    // (counts[MW_TIME_MARKER]: a parsed time filter_grep's decoder would read as a group marker -- the unfused kernels restate that, the pair does not)
+    if (!ahead && (n == 0 || hm.counts[MW_EXACT] > 0 || hm.ov_count > 0 || hm.counts[MW_TIME_MARKER] > 0)) return 0;           // (records for k_parser_emit_exact: unfused)
     const int cus = g_cus > 0 ? g_cus : 256;
     PgDecideArgs da;
     memset(&da, 0, sizeof(da));
@@ -2307,7 +2329,7 @@ static int run_pair_fused(flbgpu_filter *fp, flbgpu_filter *fg, const flbgpu_dev
     }
     da.keep_len = pc.keep_len; da.counts = dm->counts;
     // rows the inline evaluation left open (unparsed records, records of the generic kernel, rules on a kept time field)
-    if (ahead || hm.counts[7] > 0 || hm.counts[2] > 0) { ProfScope ps(fp, st, "k_pg_decide"); launch_pg_decide(da, cus, st); }
+    if (ahead || hm.counts[MW_PG_PENDING] > 0 || hm.counts[MW_GENERIC] > 0) { ProfScope ps(fp, st, "k_pg_decide"); launch_pg_decide(da, cus, st); }
     { ProfScope ps(fp, st, "k_scan"); launch_scan(da.keep_len, n, fp->d_scan_tmp.as<uint64_t>(), fp->d_off.as<uint64_t>(), st); }
     total = 0;
     auto emit_args = [&](PgEmitArgs &ea) {
@@ -2321,13 +2343,13 @@ static int run_pair_fused(flbgpu_filter *fp, flbgpu_filter *fg, const flbgpu_dev
     };
     // RF_TIMEPEND rows k_pg_emit could not settle (a time text the fixed-layout plan refuses, a time the encoder refuses): the call
     // is repeated with the lookup inside the single pass, where the strptime interpreter stands behind the plan -- and stays there
-    auto defer_failed = [&](unsigned long long c13) -> bool {
+    auto defer_failed = [&](unsigned long long time_fail) -> bool {
         if (!(fp->last_path & 4u)) return false;                // (the lookup was inside the pass)
-        if (c13 == 0) { fp->defer.good(); return false; }
+        if (time_fail == 0) { fp->defer.good(); return false; }
         fp->defer.bad();
         return true;
     };
-    // the plain build of k_pg_emit: a kept record it leaves alone (counts[15]) is written by the general build behind it; when that is more
+    // the plain build of k_pg_emit: a kept record it leaves alone (counts[MW_PG_LEFT]) is written by the general build behind it; when that is more
     // than 1 kept record in 16 the general build alone runs the next calls
     auto plain_wanted = [&](const PgEmitArgs &ea) -> bool {
         const bool can = ea.ec.ok && pc.desc != nullptr && !getenv("FLBGPU_EMIT_GENERAL");
@@ -2343,28 +2365,28 @@ static int run_pair_fused(flbgpu_filter *fp, flbgpu_filter *fg, const flbgpu_dev
         PgEmitArgs ea;
         emit_args(ea);
         ea.out_cap = fg->d_out.cap - 16;
-        // (the plain build when the parser's fields are plain strings and the descriptors exist; a record it does not take -- counts[15] --
+        // (the plain build when the parser's fields are plain strings and the descriptors exist; a record it does not take -- counts[MW_PG_LEFT] --
         // sends the call round again the usual way, where the general build follows)
         const bool plain_emit = plain_wanted(ea);
         { ProfScope ps(fp, st, "k_pg_emit"); if (plain_emit) launch_pg_emit_plain(ea, d0.nfields, cus, st); else launch_pg_emit(ea, d0.nfields, cus, st); }
         uint8_t *sink = g_spec.last ? g_spec.sink : nullptr;
         launch_finish_to_host(ea.out, ea.out_cap, ea.out_off + n, sink, g_spec.sink_cap, dm, &hm, (uint32_t) sizeof(hm), &total, st);
         if (hipStreamSynchronize(st) != hipSuccess) return -1;
-        if (plain_emit) plain_result(hm.counts[15], hm.counts[5]);
-        if (defer_failed(hm.counts[13]) || (plain_emit && hm.counts[15] > 0) || !ahead_counters_ok(fp, hm, n) || hm.counts[3] > 0 || hm.counts[14] > 0 || hm.ov_count > 0 || total > ea.out_cap) {
+        if (plain_emit) plain_result(hm.counts[MW_PG_LEFT], hm.counts[MW_PG_KEEP]);
+        if (defer_failed(hm.counts[MW_PG_TIME_FAIL]) || (plain_emit && hm.counts[MW_PG_LEFT] > 0) || !ahead_counters_ok(fp, hm, n) || hm.counts[MW_EXACT] > 0 || hm.counts[MW_TIME_MARKER] > 0 || hm.ov_count > 0 || total > ea.out_cap) {
             SpecOff usual;
             return run_pair_fused(fp, fg, in, out, stats2);
         }
-        if (hm.counts[6] == 0 || hm.counts[5] == hm.counts[6]) return 0;
-        fp->last_in = hm.counts[0]; fp->last_out = hm.counts[6];
-        fg->last_in = hm.counts[6]; fg->last_out = hm.counts[5];
+        if (hm.counts[MW_PG_OUT] == 0 || hm.counts[MW_PG_KEEP] == hm.counts[MW_PG_OUT]) return 0;
+        fp->last_in = hm.counts[MW_DECODED]; fp->last_out = hm.counts[MW_PG_OUT];
+        fg->last_in = hm.counts[MW_PG_OUT]; fg->last_out = hm.counts[MW_PG_KEEP];
         if (stats2) {
-            stats2[0].ret = FLBGPU_FILTER_MODIFIED; stats2[0].in_records = hm.counts[0]; stats2[0].out_records = hm.counts[6]; stats2[0].out_bytes = hm.counts[4];
-            stats2[1].ret = FLBGPU_FILTER_MODIFIED; stats2[1].in_records = hm.counts[6]; stats2[1].out_records = hm.counts[5]; stats2[1].out_bytes = total;
+            stats2[0].ret = FLBGPU_FILTER_MODIFIED; stats2[0].in_records = hm.counts[MW_DECODED]; stats2[0].out_records = hm.counts[MW_PG_OUT]; stats2[0].out_bytes = hm.counts[MW_PG_BYTES];
+            stats2[1].ret = FLBGPU_FILTER_MODIFIED; stats2[1].in_records = hm.counts[MW_PG_OUT]; stats2[1].out_records = hm.counts[MW_PG_KEEP]; stats2[1].out_bytes = total;
         }
         memset(out, 0, sizeof(*out));
         if (total == 0) return 1;
-        out->data = fg->d_out.p; out->row_off = fp->d_off.as<uint64_t>(); out->n = n; out->bytes = total;
+        set_out(fg, fp, out, n, total);
         if (sink && total <= g_spec.sink_cap) g_spec.sunk = true;
         return 1;
     }
@@ -2373,12 +2395,12 @@ static int run_pair_fused(flbgpu_filter *fp, flbgpu_filter *fg, const flbgpu_dev
         hipStreamSynchronize(st) != hipSuccess) return -1;
     // a parser that emits nothing (NOTOUCH: grep would see the ORIGINAL chunk) or a grep that keeps everything
     // (NOTOUCH: the chain's output is the parser's): the unfused kernels
-    if (hm.counts[6] == 0 || hm.counts[5] == hm.counts[6] || hm.counts[14] > 0) return 0;
-    fp->last_in = hm.counts[0]; fp->last_out = hm.counts[6];
-    fg->last_in = hm.counts[6]; fg->last_out = hm.counts[5];
+    if (hm.counts[MW_PG_OUT] == 0 || hm.counts[MW_PG_KEEP] == hm.counts[MW_PG_OUT] || hm.counts[MW_TIME_MARKER] > 0) return 0;
+    fp->last_in = hm.counts[MW_DECODED]; fp->last_out = hm.counts[MW_PG_OUT];
+    fg->last_in = hm.counts[MW_PG_OUT]; fg->last_out = hm.counts[MW_PG_KEEP];
     if (stats2) {
-        stats2[0].ret = FLBGPU_FILTER_MODIFIED; stats2[0].in_records = hm.counts[0]; stats2[0].out_records = hm.counts[6]; stats2[0].out_bytes = hm.counts[4];
-        stats2[1].ret = FLBGPU_FILTER_MODIFIED; stats2[1].in_records = hm.counts[6]; stats2[1].out_records = hm.counts[5]; stats2[1].out_bytes = total;
+        stats2[0].ret = FLBGPU_FILTER_MODIFIED; stats2[0].in_records = hm.counts[MW_DECODED]; stats2[0].out_records = hm.counts[MW_PG_OUT]; stats2[0].out_bytes = hm.counts[MW_PG_BYTES];
+        stats2[1].ret = FLBGPU_FILTER_MODIFIED; stats2[1].in_records = hm.counts[MW_PG_OUT]; stats2[1].out_records = hm.counts[MW_PG_KEEP]; stats2[1].out_bytes = total;
     }
     memset(out, 0, sizeof(*out));
     if (total == 0) return 1;                               // every record dropped: MODIFIED with an empty output
@@ -2387,18 +2409,21 @@ static int run_pair_fused(flbgpu_filter *fp, flbgpu_filter *fg, const flbgpu_dev
     emit_args(ea);
     const bool plain_emit = plain_wanted(ea);
     { ProfScope ps(fp, st, "k_pg_emit"); if (plain_emit) launch_pg_emit_plain(ea, d0.nfields, cus, st); else launch_pg_emit(ea, d0.nfields, cus, st); }
-    unsigned long long *c13 = (unsigned long long *) (fp->hp_misc.as<uint8_t>() + sizeof(MiscWords) + sizeof(uint64_t));     // counts[13 .. 15]
-    c13[0] = c13[1] = c13[2] = 0;
-    if (hipMemcpyAsync(c13, &dm->counts[13], 3 * sizeof(unsigned long long), hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
+    // what k_pg_emit counted, MW_PG_TIME_FAIL .. MW_PG_LEFT, behind the size in the page-locked block
+    enum { LATE0 = MW_PG_TIME_FAIL, NLATE = MW_PG_LEFT - MW_PG_TIME_FAIL + 1 };
+    static_assert(1 + NLATE <= MISC_TAIL, "the fused pair's late counters fit behind the size");
+    unsigned long long *late = (unsigned long long *) (misc_tail(hmp) + 1);
+    memset(late, 0, NLATE * sizeof(*late));
+    if (hipMemcpyAsync(late, &dm->counts[LATE0], NLATE * sizeof(*late), hipMemcpyDeviceToHost, st) != hipSuccess) return -1;
     if (hipStreamSynchronize(st) != hipSuccess) return -1;
-    if (defer_failed(c13[0])) return run_pair_fused(fp, fg, in, out, stats2);
-    if (plain_emit) plain_result(c13[2], hm.counts[5]);
-    if (plain_emit && c13[2] > 0) {
+    if (defer_failed(late[MW_PG_TIME_FAIL - LATE0])) return run_pair_fused(fp, fg, in, out, stats2);
+    if (plain_emit) plain_result(late[MW_PG_LEFT - LATE0], hm.counts[MW_PG_KEEP]);
+    if (plain_emit && late[MW_PG_LEFT - LATE0] > 0) {
         // records the plain build left alone (no descriptor, another parser's, larger than its staging area): the general build over the chunk
         { ProfScope ps(fp, st, "k_pg_emit_general"); launch_pg_emit(ea, d0.nfields, cus, st); }
         if (hipStreamSynchronize(st) != hipSuccess) return -1;
     }
-    out->data = fg->d_out.p; out->row_off = fp->d_off.as<uint64_t>(); out->n = n; out->bytes = total;
+    set_out(fg, fp, out, n, total);
     return 1;
 }
 
@@ -2538,6 +2563,15 @@ static int chain_dev(flbgpu_filter *const *filters, int n, const flbgpu_dev_chun
                      flbgpu_chain_stat *stats) {
     flbgpu_dev_chunk cur = *in;
     bool modified = false;
+    // the MODIFIED output of stage `last` becomes the working chunk; an empty one (all records removed, no data to continue processing)
+    // zeroes the stats of the stages behind it and ends the chain: false
+    auto take = [&](const flbgpu_dev_chunk &o, int last) -> bool {
+        modified = true;
+        cur = o;
+        if (o.bytes != 0) return true;
+        if (stats) for (int j = last + 1; j < n; j++) memset(&stats[j], 0, sizeof(stats[j]));
+        return false;
+    };
     for (int i = 0; i < n; i++) {
         flbgpu_dev_chunk o;
         memset(&o, 0, sizeof(o));
@@ -2550,13 +2584,8 @@ static int chain_dev(flbgpu_filter *const *filters, int n, const flbgpu_dev_chun
             const int fr = run_pair_fused(filters[i], filters[i + 1], &cur, &o, s2);
             if (fr == 1) {
                 if (stats) { stats[i] = s2[0]; stats[i + 1] = s2[1]; }
-                modified = true;
-                cur = o;
                 i++;
-                if (o.bytes == 0) {
-                    if (stats) for (int j = i + 1; j < n; j++) { memset(&stats[j], 0, sizeof(stats[j])); }
-                    break;
-                }
+                if (!take(o, i)) break;
                 continue;
             }
             if (fr < 0) {
@@ -2574,12 +2603,7 @@ static int chain_dev(flbgpu_filter *const *filters, int n, const flbgpu_dev_chun
                 const bool mod = s2[0].ret == FLBGPU_FILTER_MODIFIED || s2[1].ret == FLBGPU_FILTER_MODIFIED;
                 i++;
                 if (!mod) continue;
-                modified = true;
-                cur = o;
-                if (o.bytes == 0) {
-                    if (stats) for (int j = i + 1; j < n; j++) { memset(&stats[j], 0, sizeof(stats[j])); }
-                    break;
-                }
+                if (!take(o, i)) break;
                 continue;
             }
         }
@@ -2595,12 +2619,7 @@ static int chain_dev(flbgpu_filter *const *filters, int n, const flbgpu_dev_chun
         // filter_multiline's -1 ("this chunk belongs to the CPU plugin, whose stream then owns the rule state") ends a chain of any length
         if (ret < 0 && (n == 1 || filters[i]->kind == F_MLFILTER)) { *out = cur; return ret; }
         if (ret != FLBGPU_FILTER_MODIFIED) continue;
-        modified = true;
-        cur = o;
-        if (o.bytes == 0) {                     // all records removed, no data to continue processing
-            if (stats) for (int j = i + 1; j < n; j++) { memset(&stats[j], 0, sizeof(stats[j])); }
-            break;
-        }
+        if (!take(o, i)) break;
     }
     *out = cur;
     return modified ? FLBGPU_FILTER_MODIFIED : FLBGPU_FILTER_NOTOUCH;
@@ -2742,7 +2761,7 @@ extern "C" int flbgpu_host_phases(double *out, int cap) {
 
 static bool stage_init(flbgpu_filter *f) {
     for (int i = 0; i < 2; i++) {
-        if (!f->ev_stage[i] && hipEventCreateWithFlags(&f->ev_stage[i], hipEventDisableTiming) != hipSuccess) return false;
+        if (!f->ev_stage[i] && hipEventCreateWithFlags(&f->ev_stage[i].h, hipEventDisableTiming) != hipSuccess) return false;
     }
     return true;
 }

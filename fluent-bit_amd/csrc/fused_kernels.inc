@@ -48,7 +48,7 @@ __global__ void __launch_bounds__(256) k_pg_decide(PgDecideArgs a) {
             bool keep;
             if (flags & RF_PARSED) {
                 // (a parsed time that reads as a group marker to filter_grep's decoder: tile_kernels.inc k_parser_reg)
-                if (a.info[4 * nc + r] >= 0xfffffffeu) atomicAdd(&a.counts[14], 1ull);
+                if (a.info[4 * nc + r] >= 0xfffffffeu) atomicAdd(&a.counts[MW_TIME_MARKER], 1ull);
                 CapsView cv;
                 cv.base = a.caps; cv.n = nc; cv.r = r;
                 keep = pg_grep_parsed(a.rules, a.nrules, a.logical_op, a.rule_fmask, a.rule_lds_off, drop_m, rec + val_off, cv, lds);
@@ -71,9 +71,9 @@ __global__ void __launch_bounds__(256) k_pg_decide(PgDecideArgs a) {
         n_out += __shfl_down(n_out, o, 64); n_keep += __shfl_down(n_keep, o, 64); out_bytes += __shfl_down(out_bytes, o, 64);
     }
     if (lane == 0) {
-        if (out_bytes) atomicAdd(&a.counts[4], out_bytes);
-        if (n_keep) atomicAdd(&a.counts[5], (unsigned long long) n_keep);
-        if (n_out) atomicAdd(&a.counts[6], (unsigned long long) n_out);
+        if (out_bytes) atomicAdd(&a.counts[MW_PG_BYTES], out_bytes);
+        if (n_keep) atomicAdd(&a.counts[MW_PG_KEEP], (unsigned long long) n_keep);
+        if (n_out) atomicAdd(&a.counts[MW_PG_OUT], (unsigned long long) n_out);
     }
 }
 
@@ -102,7 +102,7 @@ __device__ __noinline__ bool pge_time(const uint8_t *data, uint64_t bytes, uint6
 // PLAIN (round 5): the build for what the single pass leaves behind on ordinary data -- every kept record with its descriptor, the
 // parser's fields plain strings (EmitCfg::ok) -- WITHOUT the general writer in it: write_record (Types casts, reserved keys, decoders'
 // rows, records larger than the staging area) made the kernel 254 registers wide, two waves per SIMD, for code the benchmark never
-// runs.  A record the plain build does not take is counted (counts[15]) and left alone; the host then runs the general build over the
+// runs.  A record the plain build does not take is counted (counts[MW_PG_LEFT]) and left alone; the host then runs the general build over the
 // chunk (same bytes for the records both write).  Its staging area is a little smaller so that three workgroups share a CU's LDS.
 constexpr int PGE_ROWS = 512;
 constexpr int PGE_STG_GENERAL = 9728;        // staging bytes per wave (about 34 records of 275 B)
@@ -173,7 +173,7 @@ __global__ void __launch_bounds__(256) k_pg_emit(PgEmitArgs a) {
                         int64_t s2 = 0;
                         const bool tok = pge_time(a.data, a.bytes, roff + ri.val_off + tb, &ps, &s2);
                         if (tok && s2 != 0) { tsec = s2; tnsec = 0; }
-                        if (!tok || encoder_refuses_time(tsec, tnsec)) atomicAdd(&a.counts[13], 1ull);
+                        if (!tok || encoder_refuses_time(tsec, tnsec)) atomicAdd(&a.counts[MW_PG_TIME_FAIL], 1ull);
                         else { ri.ts_sec = (uint32_t) tsec; ri.ts_nsec = (uint32_t) tnsec; }
                     }
                 }
@@ -197,7 +197,7 @@ __global__ void __launch_bounds__(256) k_pg_emit(PgEmitArgs a) {
                 if (direct) m = 1;
                 if constexpr (PLAIN) {
                     if (lane >= lo && lane < lo + m && o1 > o0) {
-                        if (direct || !(lds_caps && a.ec.ok && ri.parser_idx == 0 && (fl & RF_DESC))) atomicAdd(&a.counts[15], 1ull);   // the general build's
+                        if (direct || !(lds_caps && a.ec.ok && ri.parser_idx == 0 && (fl & RF_DESC))) atomicAdd(&a.counts[MW_PG_LEFT], 1ull);   // the general build's
                         else {
                             CapsLdsView cv;
                             cv.col = spans + lane; cv.stride = 64;

@@ -345,6 +345,7 @@ __global__ void __launch_bounds__(64 * GL_WAVES, GL_MINW_) k_grep_lane(GrepLaneA
         const uint32_t rowoff = rowincl - keeplen;
         if (lane < nrows) a.off_out[r0 + lane] = gbase + rowoff;
         if (lane == 0) {
+            // (a.words = &counts[MW_LANE_BYTES]: words[0] is that slot, words[1] the one behind it, MW_LANE_FAIL)
             if (!room) atomicAdd(&a.words[1], stuck ? (1ull << 32) : 1ull);
             if (live && tile == a.ntiles - 1) { a.off_out[a.g.n] = gbase + total; a.words[0] = gbase + total; }
         }
@@ -392,9 +393,9 @@ __global__ void __launch_bounds__(64 * GL_WAVES, GL_MINW_) k_grep_lane(GrepLaneA
         n_dec += __shfl_down(n_dec, o, 64); n_keep += __shfl_down(n_keep, o, 64); n_keep2 += __shfl_down(n_keep2, o, 64); bytes1 += __shfl_down(bytes1, o, 64);
     }
     if (lane == 0) {
-        if (n_dec) atomicAdd(&a.g.counts[0], (unsigned long long) n_dec);
-        if (n_keep) atomicAdd(&a.g.counts[1], (unsigned long long) n_keep);
-        if (a.two) { if (n_keep2) atomicAdd(&a.g.counts[2], (unsigned long long) n_keep2); if (bytes1) atomicAdd(&a.g.counts[3], bytes1); }
+        if (n_dec) atomicAdd(&a.g.counts[MW_DECODED], (unsigned long long) n_dec);
+        if (n_keep) atomicAdd(&a.g.counts[MW_KEPT], (unsigned long long) n_keep);
+        if (a.two) { if (n_keep2) atomicAdd(&a.g.counts[MW_KEPT2], (unsigned long long) n_keep2); if (bytes1) atomicAdd(&a.g.counts[MW_BYTES1], bytes1); }
     }
 }
 

@@ -15,8 +15,8 @@ struct GrepLaneArgs {
     unsigned long long *prof;           // measurement only (FLBGPU_GREP_PROF): [8] shader cycles per phase, summed over the waves
     uint32_t text_cap;                  // LDS bytes of a wave's records (a multiple of 16, <= grep_lane_text_max())
     // two filter_grep instances that follow each other in a chain run as ONE pass (flb_filter_do hands the second what the first keeps, and
-    // grep changes no record): g2 = the second filter's rules (its table offsets count on behind the first's; counts[2] = what it keeps,
-    // counts[3] = the bytes the first keeps); the slots below are the names of both
+    // grep changes no record): g2 = the second filter's rules (its table offsets count on behind the first's; counts[MW_KEPT2] = what it
+    // keeps, counts[MW_BYTES1] = the bytes the first keeps); the slots below are the names of both
     int two;
     GrepArgs g2;
     int nslots;                         // names in slot_kw / slot_klen (GrepArgs::rule_slot of both filters index them)

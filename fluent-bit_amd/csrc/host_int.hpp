@@ -46,8 +46,8 @@ struct DevBuf {
     void release() { if (p) (void) hipFree(p); p = nullptr; cap = 0; }
     template <class T> T *as() const { return (T *) p; }
 };
-// a device buffer that releases itself: function-local ones on every return path, and the members of a FilterState with their owner
-// (DevBuf itself is a plain member type that its owner releases by hand)
+// a device buffer that releases itself: function-local ones on every return path, and the members of a flbgpu_filter, a FilterState
+// or an L2mState with their owner (DevBuf itself is the plain view of one that functions take)
 struct ScopedDevBuf : DevBuf {
     ScopedDevBuf() = default;
     ScopedDevBuf(const ScopedDevBuf &) = delete;
@@ -78,6 +78,17 @@ struct ScopedPinnedBuf : PinnedBuf {
     ScopedPinnedBuf &operator=(const ScopedPinnedBuf &) = delete;
     ~ScopedPinnedBuf() { release(); }
 };
+// a stream or an event that is destroyed with its owner; reads as the handle it holds, `h` is what the create call fills
+template <class H, hipError_t (*Destroy)(H)> struct HipHandle {
+    H h = nullptr;
+    HipHandle() = default;
+    HipHandle(const HipHandle &) = delete;
+    HipHandle &operator=(const HipHandle &) = delete;
+    ~HipHandle() { if (h) (void) Destroy(h); }
+    operator H() const { return h; }
+};
+using StreamHandle = HipHandle<hipStream_t, hipStreamDestroy>;
+using EventHandle = HipHandle<hipEvent_t, hipEventDestroy>;
 
 // uploads vectors of one table set into a single device allocation
 struct TableBlob {
@@ -111,8 +122,10 @@ struct RaPart {
     DevKey key = {};                    // RA_KEY
 };
 int ra_split(const std::string &a, std::vector<RaPart> &parts, std::string &why);
+// a compiled pattern's match-only tables (ascii DFA, what stands behind it) uploaded into two new blobs (flbgpu.cpp)
+bool upload_rule(const rx::Program &prog, GrepRule &r, std::vector<std::unique_ptr<TableBlob>> &blobs);
 // "<field> <regex>" rule of filter_grep / filter_log_to_metrics -> device rule (tables uploaded into blobs)
-bool compile_rule(const std::string &ra_field, const char *pattern, GrepRule &r, std::vector<TableBlob *> &blobs, std::string &why, bool *nonregular = nullptr);
+bool compile_rule(const std::string &ra_field, const char *pattern, GrepRule &r, std::vector<std::unique_ptr<TableBlob>> &blobs, std::string &why, bool *nonregular = nullptr);
 
 }  // namespace flbgpu
 
@@ -125,13 +138,13 @@ struct L2mState {
     std::vector<std::string> label_keys;
     std::vector<flbgpu::DevKey> labels;
     flbgpu::DevKey value_key;
-    flbgpu::DevBuf d_labels, d_value_key, d_bounds;
+    flbgpu::ScopedDevBuf d_labels, d_value_key, d_bounds;
     // series dictionary + rows
     uint64_t cap = 0, arena_cap = 0;
     uint32_t max_series = 0;
-    flbgpu::DevBuf d_slot_hash, d_slot_sid, d_arena, d_key_off, d_key_len, d_series_hash, d_rows, d_ctr;
+    flbgpu::ScopedDevBuf d_slot_hash, d_slot_sid, d_arena, d_key_off, d_key_len, d_series_hash, d_rows, d_ctr;
     // per-call columns
-    flbgpu::DevBuf d_sid, d_val, d_tmp, d_misc;
+    flbgpu::ScopedDevBuf d_sid, d_val, d_tmp, d_misc;
     uint64_t idx_base = 0;
     uint64_t last_obs = 0, last_deferred = 0, last_stale = 0, grows = 0;
     // sum_order reference (flbgpu_l2m_set_sum_order): next to the exact sum, the histogram sum as cmetrics builds it -- one f64
@@ -140,15 +153,14 @@ struct L2mState {
     // and the flush folds them rank after rank, each rank continuing from the sums the rank in front ended on (l2m.cpp "the chain"):
     // the bits of ONE process that was fed rank 0's records of the interval, then rank 1's ... -- for any number of ranks
     int sum_order_ref = 1;                                   // (round 6: the reference's order is the default of the C ABI too, as it is the plugin shim's)
-    flbgpu::DevBuf d_seq;
+    flbgpu::ScopedDevBuf d_seq;
     uint32_t seq_cap = 0;
-    flbgpu::DevBuf d_log_sid, d_log_val, d_nobad, d_seqwork;
+    flbgpu::ScopedDevBuf d_log_sid, d_log_val, d_nobad, d_seqwork;
     uint64_t log_n = 0, log_cap = 0;
     std::unordered_map<std::string, double> chain_sums;      // per label tuple: the sum the last flush ended on (the same on every rank)
     std::vector<double> last_chain;                          // the last flush's sums in the order of its output
 };
 
-void l2m_state_destroy(L2mState *);
 flbgpu::L2mTable l2m_table_of(L2mState *s);
 bool l2m_table_init(L2mState *s);
 bool l2m_table_grow(L2mState *s, hipStream_t st);
@@ -173,11 +185,11 @@ struct FilterState {
 
 struct flbgpu_filter {
     int kind = 0;
-    hipStream_t stream = nullptr;
+    flbgpu::StreamHandle stream;      // first: whatever the members below hold is released before the stream goes
     // filter_parser
     flbgpu::FParserCfg pcfg;
     std::vector<flbgpu_parser *> parsers;
-    flbgpu::DevBuf d_parsers;
+    flbgpu::ScopedDevBuf d_parsers;
     uint32_t caps_stride = 0;
     // The choices between a fast build and the build that takes everything are made per call from what the last calls showed -- no
     // choice is for good (round 5's latches: one odd chunk moved a filter to the slower build for the life of the process):
@@ -221,15 +233,15 @@ struct flbgpu_filter {
     uint64_t dec_launch[5] = {0, 0, 0, 0, 0};
     // filter_grep (and the rule gate of filter_log_to_metrics)
     std::vector<flbgpu::GrepRule> rules;
-    std::vector<flbgpu::TableBlob *> rule_blobs;
+    std::vector<std::unique_ptr<flbgpu::TableBlob>> rule_blobs;
     // host rules (flbgpu.cpp): rules[i] whose pattern is not a regular expression -- host_rx[i] is the backtracking matcher's program
     // (rx.hpp bt_compile), nullptr for a device rule; values the matcher gave up on (its backtrack budget); filter_parser: records the
     // host parser did not take (duplicate Key_Name entries, values of 64 KB and more)
     std::vector<rx::BtProgram *> host_rx;
     bool has_host_rules = false;
-    flbgpu::DevBuf d_hspans, d_hbits;
+    flbgpu::ScopedDevBuf d_hspans, d_hbits;
     uint64_t host_budget_over = 0, host_unhandled = 0, host_values = 0;
-    flbgpu::DevBuf d_rules;
+    flbgpu::ScopedDevBuf d_rules;
     int logical_op = 0;
     // filter_log_to_metrics
     L2mState *l2m = nullptr;
@@ -244,40 +256,33 @@ struct flbgpu_filter {
     const void *rtag_dev_base = nullptr;
     const uint8_t *rtag_host_base = nullptr;
     bool host_list = false;                     // filter_parser: a list of several parsers with host parsers in it (flbgpu.cpp host_list_rx)
-    flbgpu::DevBuf d_hres[flbgpu::MAX_HOST_PARSERS];   // their answers for the chunk at hand
+    flbgpu::ScopedDevBuf d_hres[flbgpu::MAX_HOST_PARSERS];   // their answers for the chunk at hand
     // msgpack -> JSON output formatter (packfmt.cpp)
     flbgpu::JsonFmtCfg jcfg = {};
-    flbgpu::DevBuf d_datekey, d_grow;
+    flbgpu::ScopedDevBuf d_datekey, d_grow;
     // working buffers
-    flbgpu::DevBuf d_info, d_caps, d_null, d_len, d_off, d_scan_tmp, d_out, d_rid, d_rid2, d_misc, d_status, d_out_off, d_ov, d_kept, d_keep, d_pg, d_args, d_desc, d_tail, d_dec, d_fix, d_units, d_perm, d_permwork;
-    flbgpu::DevBuf h_in_data, h_in_off;        // device copies of host input (flbgpu_filter_run)
-    flbgpu::PinnedBuf hp_misc, hp_args, hp_off, hp_stage[2];    // pinned record offsets / two staging slabs
-    hipEvent_t ev_stage[2] = {nullptr, nullptr};
+    flbgpu::ScopedDevBuf d_info, d_caps, d_null, d_len, d_off, d_scan_tmp, d_out, d_rid, d_rid2, d_misc, d_status, d_out_off, d_ov, d_kept, d_keep, d_pg, d_args, d_desc, d_tail, d_dec, d_fix, d_units, d_perm, d_permwork;
+    flbgpu::ScopedDevBuf h_in_data, h_in_off;        // device copies of host input (flbgpu_filter_run)
+    flbgpu::ScopedPinnedBuf hp_misc, hp_args, hp_off, hp_stage[2];    // pinned record offsets / two staging slabs
+    flbgpu::EventHandle ev_stage[2];
     flbgpu_indexer *indexer = nullptr;        // device record indexer of the host-level call (large chunks)
     uint64_t last_in = 0, last_out = 0;
     // profiling
     bool prof = false;
     std::vector<KernelProf> kp;
     std::vector<ProfPending> pending;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    flbgpu::EventHandle ev0, ev1;
+    // Order of release: this body first -- the pending profile pairs, then the states and the gate filter this one owns (their buffers are
+    // their own, as is the gate's stream), then the indexer (likewise) -- and then the members in reverse order: ev0 / ev1, the
+    // staging events, the pinned and the device buffers, the rule tables, the stream last.  Against the hand-kept list this replaces,
+    // the filter's own events now go behind its states and the indexer in front of its buffers; none of them refers to another.
     ~flbgpu_filter() {
         for (auto &p : pending) { (void) hipEventDestroy(p.e0); (void) hipEventDestroy(p.e1); }
-        if (l2m) l2m_state_destroy(l2m);
+        delete l2m;
         delete state;
-        for (auto *b : rule_blobs) delete b;
         for (auto *b : host_rx) if (b) rx::bt_free(b);
         delete l2m_gate;
-        d_hspans.release(); d_hbits.release();
-        for (auto &b : d_hres) b.release();
-        flbgpu::DevBuf *all[] = {&d_parsers, &d_rules, &d_info, &d_caps, &d_null, &d_len, &d_off, &d_scan_tmp, &d_out, &d_rid, &d_rid2,
-                                 &d_misc, &d_status, &d_out_off, &d_ov, &d_kept, &d_keep, &d_pg, &h_in_data, &h_in_off, &d_datekey, &d_grow, &d_args, &d_desc, &d_tail, &d_dec, &d_fix, &d_units, &d_perm, &d_permwork};
-        for (auto *b : all) b->release();
         if (indexer) flbgpu_indexer_destroy(indexer);
-        hp_misc.release(); hp_args.release(); hp_off.release(); hp_stage[0].release(); hp_stage[1].release();
-        for (auto &e : ev_stage) if (e) (void) hipEventDestroy(e);
-        if (ev0) (void) hipEventDestroy(ev0);
-        if (ev1) (void) hipEventDestroy(ev1);
-        if (stream) (void) hipStreamDestroy(stream);
     }
 };
 

@@ -2378,7 +2378,7 @@ DEV uint32_t locate_core(const ParserMatchArgs &a, uint64_t r, const uint8_t *re
         return 0;
     }
     if (ncand == 1 && a.caps_in_lds && ri.val_len < 0xFFFF && (ri.val_len / CHK_STEP + 2) <= a.chk_len) ri.flags |= RF_CAND;
-    else if (ncand >= 1) { ri.flags |= RF_GENERIC; atomicAdd(&a.counts[2], 1ull); }
+    else if (ncand >= 1) { ri.flags |= RF_GENERIC; atomicAdd(&a.counts[MW_GENERIC], 1ull); }
     // size of the record if no parser matches: 12 + canonical metadata + canonical body; an event
     // time outside the EventTime range makes the encoder reject the record
     uint32_t out_len = 0;

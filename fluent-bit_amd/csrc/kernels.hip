@@ -103,7 +103,7 @@ __global__ void __launch_bounds__(LOC_BLOCK) k_parser_locate(ParserMatchArgs a) 
         }
     }
     for (int o = 32; o > 0; o >>= 1) n_dec += __shfl_down(n_dec, o, 64);
-    if (lane == 0 && n_dec) atomicAdd(&a.counts[0], (unsigned long long) n_dec);
+    if (lane == 0 && n_dec) atomicAdd(&a.counts[MW_DECODED], (unsigned long long) n_dec);
 }
 
 // parser 0's capture program on the located values
@@ -213,7 +213,7 @@ __global__ void __launch_bounds__(MATCH_BLOCK) k_parser_rx(ParserMatchArgs a) {
         }
     }
     for (int o = 32; o > 0; o >>= 1) n_gen += __shfl_down(n_gen, o, 64);
-    if (lane == 0 && n_gen) atomicAdd(&a.counts[2], (unsigned long long) n_gen);
+    if (lane == 0 && n_gen) atomicAdd(&a.counts[MW_GENERIC], (unsigned long long) n_gen);
 }
 
 // named fields, time lookup and size of the records parser 0 matched
@@ -308,7 +308,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))
         a.info[r] = flags;
         a.info[4 * n + r] = (uint32_t) tsec; a.info[5 * n + r] = (uint32_t) tnsec;
         // a parsed time the next decoder reads as a group marker (tile_kernels.inc k_parser_reg): counted
-        if ((uint32_t) tsec >= 0xfffffffeu) atomicAdd(&a.counts[14], 1ull);
+        if ((uint32_t) tsec >= 0xfffffffeu) atomicAdd(&a.counts[MW_TIME_MARKER], 1ull);
         if (size_from_columns) {
             // 92 92 d7 00 ts(8) + metadata + map header (width of the ORIGINAL count) + fields
             const uint32_t n0 = (uint32_t) ps.nregs_minus1;
@@ -320,7 +320,7 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))
             CountSink cs;
             write_record(cs, a.cfg, a.parsers, rec, a.data + a.row_off[r + 1], ri, caps, null_mask);
             a.out_len[r] = (uint32_t) cs.n;
-            if (cs.need_exact) { a.info[r] = flags | RF_EXACT; atomicAdd(&a.counts[3], 1ull); }
+            if (cs.need_exact) { a.info[r] = flags | RF_EXACT; atomicAdd(&a.counts[MW_EXACT], 1ull); }
         }
         if (a.pg_keep_len) {
             // pair mode: the record's fate under filter_grep, settled by k_parser_rx on the spans (else k_pg_decide's)
@@ -339,11 +339,11 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 8))
         pg_bytes += __shfl_down(pg_bytes, o, 64);
     }
     if ((threadIdx.x & 63) == 0) {
-        if (n_gen) atomicAdd(&a.counts[2], (unsigned long long) n_gen);
-        if (pg_bytes) atomicAdd(&a.counts[4], pg_bytes);
-        if (pg_keep) atomicAdd(&a.counts[5], (unsigned long long) pg_keep);
-        if (pg_out) atomicAdd(&a.counts[6], (unsigned long long) pg_out);
-        if (pg_pending) atomicAdd(&a.counts[7], (unsigned long long) pg_pending);
+        if (n_gen) atomicAdd(&a.counts[MW_GENERIC], (unsigned long long) n_gen);
+        if (pg_bytes) atomicAdd(&a.counts[MW_PG_BYTES], pg_bytes);
+        if (pg_keep) atomicAdd(&a.counts[MW_PG_KEEP], (unsigned long long) pg_keep);
+        if (pg_out) atomicAdd(&a.counts[MW_PG_OUT], (unsigned long long) pg_out);
+        if (pg_pending) atomicAdd(&a.counts[MW_PG_PENDING], (unsigned long long) pg_pending);
     }
 }
 
@@ -449,7 +449,7 @@ __global__ void __launch_bounds__(256) k_parser_generic(ParserMatchArgs a) {
             continue;
         }
         ri.ts_sec = (uint32_t) tsec; ri.ts_nsec = (uint32_t) tnsec;
-        if ((ri.flags & RF_PARSED) && (uint32_t) tsec >= 0xfffffffeu) atomicAdd(&a.counts[14], 1ull);     // (a group marker to the next decoder: tile_kernels.inc k_parser_reg)
+        if ((ri.flags & RF_PARSED) && (uint32_t) tsec >= 0xfffffffeu) atomicAdd(&a.counts[MW_TIME_MARKER], 1ull);     // (a group marker to the next decoder: tile_kernels.inc k_parser_reg)
         CountSink cs;
         const bool json_won = (ri.flags & RF_PARSED) && a.parsers[ri.parser_idx].is_json && !a.parsers[ri.parser_idx].kv_format;
         if (json_won) {
@@ -457,7 +457,7 @@ __global__ void __launch_bounds__(256) k_parser_generic(ParserMatchArgs a) {
             if (cs.n) cs.need_exact = true;                    // sized with the wide walker: emitted by the same one
         }
         else write_record(cs, a.cfg, a.parsers, rec, rec_end, ri, caps, null_mask);
-        if (cs.need_exact) { ri.flags |= RF_EXACT; atomicAdd(&a.counts[3], 1ull); }
+        if (cs.need_exact) { ri.flags |= RF_EXACT; atomicAdd(&a.counts[MW_EXACT], 1ull); }
         rec_store(a.info, a.n, r, ri);
         a.null_mask[r] = null_mask;
         a.out_len[r] = (uint32_t) cs.n;
@@ -679,8 +679,8 @@ __global__ void __launch_bounds__(GREP_BLOCK) k_grep_match(GrepArgs a) {
     // one pair of atomics per wave (same-address atomics serialise at ~12 ns each)
     for (int o = 32; o > 0; o >>= 1) { n_dec += __shfl_down(n_dec, o, 64); n_keep += __shfl_down(n_keep, o, 64); }
     if (lane == 0) {
-        if (n_dec) atomicAdd(&a.counts[0], (unsigned long long) n_dec);
-        if (n_keep) atomicAdd(&a.counts[1], (unsigned long long) n_keep);
+        if (n_dec) atomicAdd(&a.counts[MW_DECODED], (unsigned long long) n_dec);
+        if (n_keep) atomicAdd(&a.counts[MW_KEPT], (unsigned long long) n_keep);
     }
 }
 

@@ -22,14 +22,6 @@ using namespace flbgpu;
 
 struct L2mMisc { unsigned long long first_bad; unsigned long long counts[3]; };
 
-void l2m_state_destroy(L2mState *s) {
-    if (!s) return;
-    DevBuf *all[] = {&s->d_labels, &s->d_value_key, &s->d_bounds, &s->d_slot_hash, &s->d_slot_sid, &s->d_arena, &s->d_key_off,
-                     &s->d_key_len, &s->d_series_hash, &s->d_rows, &s->d_ctr, &s->d_sid, &s->d_val, &s->d_tmp, &s->d_misc, &s->d_seq, &s->d_log_sid, &s->d_log_val, &s->d_nobad, &s->d_seqwork};
-    for (auto *b : all) b->release();
-    delete s;
-}
-
 // first parser entry of flb_ra_create(str) (src/flb_record_accessor.c:74-232): text before the
 // first '$' -- or the whole string -- is a STRING part whose name is looked up as a top-level key
 // (src/record_accessor/flb_ra_parser.c:224-249); "$TAG" / "$0" entries have no key.

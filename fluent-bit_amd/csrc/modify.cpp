@@ -246,10 +246,7 @@ static bool add_rx(ModState *m, flbgpu_filter *f, const std::string &pat, int *i
     if (!check_rx(pat, true, why, &prog)) { set_err("filter_modify: %s", why.c_str()); return false; }
     GrepRule r;
     memset(&r, 0, sizeof(r));
-    auto *b1 = new TableBlob(), *b2 = new TableBlob();
-    f->rule_blobs.push_back(b1);
-    f->rule_blobs.push_back(b2);
-    if (!upload_dfa(prog.ascii, *b1, r.dfa) || !upload_utf8(prog, *b2, r.utf8)) return false;
+    if (!upload_rule(prog, r, f->rule_blobs)) return false;
     *idx = (int) m->rx.size();
     m->rx.push_back(r);
     return true;

@@ -87,7 +87,7 @@ DEV uint32_t pjson_record(const ParserMatchArgs &a, uint64_t r, const uint8_t *r
         return 0;
     }
     ri.ts_sec = (uint32_t) tsec; ri.ts_nsec = (uint32_t) tnsec;
-    if ((ri.flags & RF_PARSED) && (uint32_t) tsec >= 0xfffffffeu) atomicAdd(&a.counts[14], 1ull);     // (a group marker to the next decoder: tile_kernels.inc k_parser_reg)
+    if ((ri.flags & RF_PARSED) && (uint32_t) tsec >= 0xfffffffeu) atomicAdd(&a.counts[MW_TIME_MARKER], 1ull);     // (a group marker to the next decoder: tile_kernels.inc k_parser_reg)
     CapsView caps;
     caps.base = a.caps; caps.n = a.n; caps.r = r;
     CountSink cs;
@@ -163,8 +163,8 @@ __global__ void __launch_bounds__(PJ_BLOCK) k_pjson_size(ParserMatchArgs a) {
     }
     for (int o = 32; o > 0; o >>= 1) { n_dec += __shfl_down(n_dec, o, 64); n_gen += __shfl_down(n_gen, o, 64); }
     if (lane == 0) {
-        if (n_dec) atomicAdd(&a.counts[0], (unsigned long long) n_dec);
-        if (n_gen) atomicAdd(&a.counts[2], (unsigned long long) n_gen);
+        if (n_dec) atomicAdd(&a.counts[MW_DECODED], (unsigned long long) n_dec);
+        if (n_gen) atomicAdd(&a.counts[MW_GENERIC], (unsigned long long) n_gen);
     }
 }
 
@@ -178,8 +178,8 @@ __global__ void __launch_bounds__(64) k_pjson_size_generic(ParserMatchArgs a) {
         uint32_t ol = pjson_record<true, JSON_GENERIC_WORDS>(a, r, a.data + a.row_off[r], a.data + a.row_off[r + 1], slot, n_dec, defer);
         // (defer can only mean "deeper than 4096 levels" here: the value is treated as unparsable)
         a.out_len[r] = ol;
-        if (ol) { a.info[r] |= RF_EXACT; atomicAdd(&a.counts[3], 1ull); }
-        if (n_dec) atomicAdd(&a.counts[0], (unsigned long long) n_dec);
+        if (ol) { a.info[r] |= RF_EXACT; atomicAdd(&a.counts[MW_EXACT], 1ull); }
+        if (n_dec) atomicAdd(&a.counts[MW_DECODED], (unsigned long long) n_dec);
     }
 }
 

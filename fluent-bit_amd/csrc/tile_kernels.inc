@@ -180,7 +180,7 @@ __global__ void __launch_bounds__(512) k_parser_tile(ParserMatchArgs a) {
                 if (direct) { rec = recg; rec_end = a.data + o1; }
                 else { rec_lds = align + (uint32_t) (o0 - g0); rec = (const uint8_t *) (tile + rec_lds); rec_end = rec + (o1 - o0); }
                 out_len = locate_core(a, r, rec, rec_end, n_dec, ri);
-                if (direct && (ri.flags & RF_CAND)) { ri.flags = (ri.flags & ~(uint32_t) RF_CAND) | RF_GENERIC; atomicAdd(&a.counts[2], 1ull); }
+                if (direct && (ri.flags & RF_CAND)) { ri.flags = (ri.flags & ~(uint32_t) RF_CAND) | RF_GENERIC; atomicAdd(&a.counts[MW_GENERIC], 1ull); }
             }
             const bool cand = act && (ri.flags & RF_CAND);
             const uint32_t vlen = ri.val_len;
@@ -286,7 +286,7 @@ __global__ void __launch_bounds__(512) k_parser_tile(ParserMatchArgs a) {
                         }
                         else {
                             ri.ts_sec = (uint32_t) tsec; ri.ts_nsec = (uint32_t) tnsec;
-                            if ((uint32_t) tsec >= 0xfffffffeu) atomicAdd(&a.counts[14], 1ull);     // (k_parser_reg: the next filter's decoder reads a group marker)
+                            if ((uint32_t) tsec >= 0xfffffffeu) atomicAdd(&a.counts[MW_TIME_MARKER], 1ull);     // (k_parser_reg: the next filter's decoder reads a group marker)
                             const uint32_t n0 = (uint32_t) ps.nregs_minus1;
                             out_len = 12 + ri.meta_canon + (n0 < 16 ? 1 : n0 < 65536 ? 3 : 5) + body_bytes;
                             if (a.pg_keep_len) {
@@ -339,14 +339,14 @@ __global__ void __launch_bounds__(512) k_parser_tile(ParserMatchArgs a) {
         pg_bytes += __shfl_down(pg_bytes, o, 64);
     }
     if (lane == 0) {
-        if (n_dec) atomicAdd(&a.counts[0], (unsigned long long) n_dec);
-        if (n_gen) atomicAdd(&a.counts[2], (unsigned long long) n_gen);
-        if (n_fin) atomicAdd(&a.counts[8], (unsigned long long) n_fin);
-        if (n_slow) atomicAdd(&a.counts[9], (unsigned long long) n_slow);
-        if (pg_bytes) atomicAdd(&a.counts[4], pg_bytes);
-        if (pg_keep) atomicAdd(&a.counts[5], (unsigned long long) pg_keep);
-        if (pg_out) atomicAdd(&a.counts[6], (unsigned long long) pg_out);
-        if (pg_pending) atomicAdd(&a.counts[7], (unsigned long long) pg_pending);
+        if (n_dec) atomicAdd(&a.counts[MW_DECODED], (unsigned long long) n_dec);
+        if (n_gen) atomicAdd(&a.counts[MW_GENERIC], (unsigned long long) n_gen);
+        if (n_fin) atomicAdd(&a.counts[MW_FINISH], (unsigned long long) n_fin);
+        if (n_slow) atomicAdd(&a.counts[MW_SLOW], (unsigned long long) n_slow);
+        if (pg_bytes) atomicAdd(&a.counts[MW_PG_BYTES], pg_bytes);
+        if (pg_keep) atomicAdd(&a.counts[MW_PG_KEEP], (unsigned long long) pg_keep);
+        if (pg_out) atomicAdd(&a.counts[MW_PG_OUT], (unsigned long long) pg_out);
+        if (pg_pending) atomicAdd(&a.counts[MW_PG_PENDING], (unsigned long long) pg_pending);
     }
 }
 
@@ -578,7 +578,7 @@ DEV bool reg_fast_decode(const uint32_t (&hw)[12], uint32_t klen, const char *ke
     ri.body_off = MAP32 ? 17 : 13; ri.body_len = rlen - ri.body_off;
     ri.val_off = voff; ri.val_len = vl; ri.key_index = 0; ri.ts_sec = sec; ri.ts_nsec = nsec;
     if (caps_in_lds && vl < 0xFFFF && (vl / CHK_STEP + 2) <= chk_len) ri.flags |= RF_CAND;
-    else { ri.flags |= RF_GENERIC; atomicAdd(&counts[2], 1ull); }
+    else { ri.flags |= RF_GENERIC; atomicAdd(&counts[MW_GENERIC], 1ull); }
     // the record if no parser matches: 92 92 d7 00 ts(8) 80 | 81 key value, canonical headers
     out_len = 12 + 1 + 1 + (1 + klen) + (vl < 32 ? 1 : vl < 256 ? 2 : vl < 65536 ? 3 : 5) + vl;
     return true;
@@ -887,7 +887,7 @@ __global__ void __launch_bounds__(TB) k_parser_reg(ParserMatchArgs a) {
             }
             if (!fast) {
                 if constexpr (SLOW) out_len = a.self ? locate_core_ool(a.self, r, recg, a.data + o1, &n_dec, &ri) : locate_core(a, r, recg, a.data + o1, n_dec, ri);
-                else { n_loc++; a.info[r] = RF_NEEDLOC; act = false; to_fix = true; if (!listed) atomicMax(&a.counts[11], (unsigned long long) (n - r)); }   // the fix-up launch takes the row
+                else { n_loc++; a.info[r] = RF_NEEDLOC; act = false; to_fix = true; if (!listed) atomicMax(&a.counts[MW_FIX_SPAN], (unsigned long long) (n - r)); }   // the fix-up launch takes the row
             }
             else if ((ri.flags & RF_CAND) && !(a.debug_skip & 2) && !STREAMW) qfilled = true;
         }
@@ -1331,10 +1331,10 @@ __global__ void __launch_bounds__(TB) k_parser_reg(ParserMatchArgs a) {
                         ri.ts_sec = (uint32_t) tsec; ri.ts_nsec = (uint32_t) tnsec;
                         // a parsed time of -1 s / -2 s (or 2106-02-07 06:28:14 / :15 UTC): filter_parser writes ff ff ff ff / fe .. as the
                         // timestamp, which the NEXT filter's decoder reads as a group marker -- hidden, or with nanoseconds a decoder error
-                        // (src/flb_log_event_decoder.c: kdev.inc decode_event).  Counted (counts[14]): flb_filter_do's re-count of the filter's
+                        // (src/flb_log_event_decoder.c: kdev.inc decode_event).  Counted (counts[MW_TIME_MARKER]): flb_filter_do's re-count of the filter's
                         // output does not see such a record (src/flb_filter.c:272, src/flb_mp.c:49-71), and the pair, which does not restate
                         // the next decoder's view, hands the chunk to the unfused kernels (flbgpu.cpp run_pair_fused).
-                        if ((uint32_t) tsec >= 0xfffffffeu) atomicAdd(&a.counts[14], 1ull);
+                        if ((uint32_t) tsec >= 0xfffffffeu) atomicAdd(&a.counts[MW_TIME_MARKER], 1ull);
                         const uint32_t n0 = CFG(nregs_minus1);
                         out_len = 12 + ri.meta_canon + (n0 < 16 ? 1 : n0 < 65536 ? 3 : 5) + body_bytes;
                         if (a.pg_keep_len) {
@@ -1435,18 +1435,19 @@ __global__ void __launch_bounds__(TB) k_parser_reg(ParserMatchArgs a) {
     if (!SLOW && listed && lane == 0) fix_cnt[wave_slot] = nfix;
     if (len_note) {
         for (int o = 32; o > 0; o >>= 1) len_sum += __shfl_down(len_sum, o, 64);
+        // (a.len_stat = &counts[MW_LEN_STEPS]: len_stat[0] is that slot, len_stat[1] the one behind it, MW_LEN_BYTES)
         if (lane == 0 && len_sum) { atomicAdd(&a.len_stat[0], len_max); atomicAdd(&a.len_stat[1], len_sum); }
     }
     if (lane == 0) {
-        if (n_dec) atomicAdd(&a.counts[0], (unsigned long long) n_dec);
-        if (n_gen) atomicAdd(&a.counts[2], (unsigned long long) n_gen);
-        if (n_fin) atomicAdd(&a.counts[8], (unsigned long long) n_fin);
-        if (n_slow) atomicAdd(&a.counts[9], (unsigned long long) n_slow);
-        if (n_loc) atomicAdd(&a.counts[10], (unsigned long long) n_loc);
-        if (pg_bytes) atomicAdd(&a.counts[4], pg_bytes);
-        if (pg_keep) atomicAdd(&a.counts[5], (unsigned long long) pg_keep);
-        if (pg_out) atomicAdd(&a.counts[6], (unsigned long long) pg_out);
-        if (pg_pending) atomicAdd(&a.counts[7], (unsigned long long) pg_pending);
+        if (n_dec) atomicAdd(&a.counts[MW_DECODED], (unsigned long long) n_dec);
+        if (n_gen) atomicAdd(&a.counts[MW_GENERIC], (unsigned long long) n_gen);
+        if (n_fin) atomicAdd(&a.counts[MW_FINISH], (unsigned long long) n_fin);
+        if (n_slow) atomicAdd(&a.counts[MW_SLOW], (unsigned long long) n_slow);
+        if (n_loc) atomicAdd(&a.counts[MW_NEEDLOC], (unsigned long long) n_loc);
+        if (pg_bytes) atomicAdd(&a.counts[MW_PG_BYTES], pg_bytes);
+        if (pg_keep) atomicAdd(&a.counts[MW_PG_KEEP], (unsigned long long) pg_keep);
+        if (pg_out) atomicAdd(&a.counts[MW_PG_OUT], (unsigned long long) pg_out);
+        if (pg_pending) atomicAdd(&a.counts[MW_PG_PENDING], (unsigned long long) pg_pending);
     }
 }
 #undef CFG
